@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — TRPO policy-update throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,7 +18,18 @@ Default workload (N=1 and the scaling runs): C4 = 8,000,000 states, obs 128,
 states are split row-wise (path-aligned), so ``scaling`` is "strong".
 
 Rank 0 prints ONE JSON line.  The timed region is K updates on the production path: the
-update's sync-free prefix replayed from its captured hipGraph.  Per-kernel times come from a
+update's sync-free prefix replayed from its captured hipGraph.
+
+A plain run does only what the headline needs: it sets the workload up, runs W warmup and K timed
+updates, writes the last timed update's outputs when ``--dump-outputs DIR`` is given, and prints
+``metric`` / ``value`` / ``unit`` / ``higher_is_better`` / ``dtype`` / ``ms_per_step`` with the
+workload's description.  ``--dump-outputs DIR`` writes what a caller of ``Engine.update`` receives
+from that update as ``DIR/<name>.npy``: ``theta`` (the new parameters), ``g``, ``stepdir`` and
+``fullstep`` in float32 and ``stats`` (the update's scalars in ``DIGEST_STATS`` order) in float64.
+The inputs are seeded, so two builds run with the same arguments can be compared file for file.
+
+Everything below is measured only with ``--full`` (``--no-cpu-baseline``, ``--cpu-rows``, ``--no-alt``,
+``--profile-steps`` and ``--profile-out`` select parts of it).  Per-kernel times come from a
 separate eager pass with per-launch HIP events on the engine's stream (events disable the
 replay; the kernels are the same launches).
 
@@ -491,6 +502,50 @@ DIGEST_STATS = ("cg_iters", "k", "reverted", "shs", "lm", "rate", "rdotr", "gdot
                 "ent_after")
 
 
+OUTPUT_VECTORS = ("theta", "g", "stepdir", "fullstep")
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def update_outputs(eng, stats) -> dict:
+    """What a caller of Engine.update() receives from the engine's last update: the new theta, the policy
+    gradient, the CG step direction and the full step (float32 [P]) and the update's scalars (`stats`, float64,
+    in DIGEST_STATS order)."""
+    from trpo_amd._lib import VEC_FULLSTEP, VEC_G, VEC_STEPDIR, VEC_THETA
+    out = {name: np.ascontiguousarray(eng.get_vector(w), dtype=np.float32)
+           for name, w in zip(OUTPUT_VECTORS, (VEC_THETA, VEC_G, VEC_STEPDIR, VEC_FULLSTEP))}
+    out["stats"] = np.array([float(stats[k]) for k in DIGEST_STATS], dtype=np.float64)
+    return out
+
+
+def dump_outputs(outputs: dict, directory: str, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """Write each array as <directory>/<name>.npy.  When the arrays together exceed `budget` bytes, every array
+    too large for an equal share is cut to a fixed sample of its elements (RandomState(0) indices, sorted: the
+    same elements in every run)."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    share = budget // max(1, len(outputs))
+    for name, a in outputs.items():
+        if total > budget and a.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def issued_arithmetic(widths) -> str:
+    """The split the update's MFMA GEMMs issue, from the engine's dispatch rules alone (no profile pass): the
+    scaled f16 hi+lo split (3 products) when option split_f16 is on and either the one-launch f16 kernels run
+    (fused16.hip) or a row GEMM takes the split path (a hidden layer wider than 128 columns, or a weight
+    gradient with more than 128 output columns); the exact bf16 hi+mid+lo split (6 products) otherwise.  The
+    --full line derives the same label from the launch tags of its profile pass."""
+    from trpo_amd._lib import get_option
+    if split_products() != 3:
+        return "bf16x6"
+    pad = lambda v: (v + 3) // 4 * 4
+    wide = (get_option("split_mfma") != 0 and any(pad(h) > 128 for h in widths[1:-1])) or \
+           (get_option("split_wg") != 0 and any(pad(b) > 128 for b in widths[1:]))
+    return "f16x3" if wide or fused16_used(widths) else "bf16x6"
+
+
 def rank_digest(vectors, stats) -> str:
     """sha256 (16 hex) over the bytes of an update's replicated outputs: theta, g, stepdir and fullstep as
     float32 arrays and the CG / step / line-search scalars (every rank must end an update
@@ -533,6 +588,43 @@ def enforce_rank_check(check: dict):
         raise SystemExit(3)
 
 
+LAST_UPDATE_KEYS = ("cg_iters", "k", "reverted", "kl_after", "surr_after")
+
+
+def headline(args, cfg, elapsed, arith, num_params, world, rehearsal, ndev) -> dict:
+    """The result line of a plain run: the headline figure over the K timed updates and what was measured."""
+    return {
+        "metric": METRIC,
+        "value": args.steps / elapsed,
+        "unit": "updates/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": f"fp32 ({arith} split)",
+        "data": "synthetic (X~N(0,1), a~U{0..A-1}, rewards~U(0,1), paths of 200 steps, "
+                "random-init policy, pi_old = p(theta_0))",
+        "config": {"workload": cfg["name"] + "; full update = discount+standardise+pg+10 CG+shs FVP+"
+                                             "line search+final losses",
+                   "n_states": cfg["n"], "obs_dim": cfg["obs"], "hidden": cfg["hidden"], "n_actions": cfg["A"],
+                   "num_params": num_params, "cg_iters": 10, "residual_tol": 0.0,
+                   "parallelism": f"dp{world} (row shards, RCCL all-reduce of [P] FVP/grad + loss scalars)"
+                   if not rehearsal or world == 1 else
+                   f"dp{world} on {ndev} GPU(s): rehearsal, ranks share GPUs, gloo host all-reduce"},
+    }
+
+
+def mark_rehearsal(out: dict, gpus_used: int) -> None:
+    """Ranks shared GPUs: not a measurement of N GPUs."""
+    out["rehearsal"] = True
+    out["n_gpus"] = gpus_used
+    out["rehearsal_updates_per_s"] = out["value"]
+    out["value"] = None
+
+
 def launch_ranks(argv, gpus: int, rehearsal: bool, visible_gpus: int) -> int:
     """`bench.py --gpus N` with no WORLD_SIZE in the environment: start N ranks on this node as one child
     process (`python -m torch.distributed.run`, rendezvous on 127.0.0.1), relay their output and return
@@ -568,19 +660,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=0, help="override total states (testing only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-rows", type=int, default=0)
-    ap.add_argument("--profile-steps", type=int, default=1, help="eager updates of the HIP-event profile pass")
-    ap.add_argument("--no-alt", action="store_true", help="skip the exact bf16x6-split comparison line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed update's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the HIP-event profile pass (roofline, FVP "
+                         "figures), the exact bf16x6-split line, the rank digest check and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-rows", type=int, default=0, help="with --full: states of the CPU baseline's sample")
+    ap.add_argument("--profile-steps", type=int, default=1,
+                    help="with --full: eager updates of the HIP-event profile pass")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the exact bf16x6-split comparison line")
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow more ranks per node than GPUs (they share GPUs through a host all-reduce)")
-    ap.add_argument("--profile-out", default="", help="write the per-tag HIP-event profile here (JSON)")
+    ap.add_argument("--profile-out", default="", help="with --full: write the per-tag HIP-event profile here (JSON)")
     ap.add_argument("--rccl-world1", action="store_true",
                     help="at one rank, still create a (one-rank) RCCL communicator: every all-reduce runs "
                          "through RCCL, and the comm block records it")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the driver's form `python bench.py --gpus N`: become the launcher of N ranks
         sys.exit(launch_ranks(sys.argv[1:], args.gpus, args.rehearsal, visible_gpu_count()))
@@ -636,11 +736,29 @@ def main():
     eng = wl.engine(comm_setup)
     comm = comm_block(eng, world, rank, rehearsal, dist)
     elapsed, last = timed_updates(eng, wl, args.steps, args.warmup, barrier)
-    digest = engine_digest(eng, last)   # after the timed region: the last timed update's outputs
+    if args.dump_outputs and rank == 0:   # the outputs are replicated: rank 0's are every rank's
+        dump_outputs(update_outputs(eng, last), args.dump_outputs)
+    # after the timed region: the last timed update's outputs (one rank has nobody to differ from)
+    digest = engine_digest(eng, last) if args.full or world > 1 else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if not args.full:
+        if digest is not None:
+            comm.update(gather_rank_check(digest, None, world, dist))
+        out = headline(args, cfg, elapsed, issued_arithmetic(widths), eng.num_params, world, rehearsal, ndev)
+        out.update({"comm": comm, "last_update": {k: last[k] for k in LAST_UPDATE_KEYS}})
+        eng.close()
+        if rank == 0:
+            if rehearsal and world > 1:
+                mark_rehearsal(out, min(ndev, local_world))
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+            enforce_rank_check(comm)
+        return
     prof = profile_pass(eng, wl, max(1, args.profile_steps))
     fvp_tags, fvp_calls = fvp_tags_per_call(prof)
     fvp_ms = sum(ms for _, (_, ms) in fvp_tags.items()) + prof.get("reduce", [0, 0])[1] * (
@@ -704,20 +822,8 @@ def main():
         wide_split = any(tag_is_split(t, widths) for t in kernel_tags if t not in ("fvp_chain", "fvp_fused"))
         fvp_prod = tag_products("fvp_fused" if "fvp_fused" in kernel_tags else "fvp_chain", widths)
         arith = ("f16x3" if prod == 3 else "bf16x6") if wide_split else ("f16x3" if fvp_prod == 3 else "bf16x6")
-        value = args.steps / elapsed
-        metric = METRIC
-        out = {
-            "metric": metric,
-            "value": value,
-            "unit": "updates/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": f"fp32 ({arith} split)",
+        out = headline(args, cfg, elapsed, arith, num_params, world, rehearsal, ndev)
+        out.update({
             "arithmetic": ("fp32 in HBM and f32 accumulation; GEMMs wider than 128 columns on f16 MFMA with each "
                            "fp32 operand scaled by a power of two and split into hi+lo f16 pieces (3 products, "
                            "error 2^-22 relative; a K-segment whose product scale is >= 14 binades below the "
@@ -729,17 +835,8 @@ def main():
                             "; the one-launch FVP (fused.hip) on the exact bf16 hi+mid+lo split (6 products)")
                            if "fvp_fused" in kernel_tags else "") +
                           "; narrower GEMMs on f32 MFMA; softmax heads and CG scalars in f64",
-            "data": "synthetic (X~N(0,1), a~U{0..A-1}, rewards~U(0,1), paths of 200 steps, "
-                    "random-init policy, pi_old = p(theta_0))",
             "timing": "timed region = K updates replayed from the captured update hipGraph (production path); "
                       "kernel times from a separate eager pass with per-launch HIP events",
-            "config": {"workload": cfg["name"] + "; full update = discount+standardise+pg+10 CG+shs FVP+"
-                                                 "line search+final losses",
-                       "n_states": N, "obs_dim": cfg["obs"], "hidden": cfg["hidden"], "n_actions": cfg["A"],
-                       "num_params": num_params, "cg_iters": 10, "residual_tol": 0.0,
-                       "parallelism": f"dp{world} (row shards, RCCL all-reduce of [P] FVP/grad + loss scalars)"
-                       if not rehearsal or world == 1 else
-                       f"dp{world} on {ndev} GPU(s): rehearsal, ranks share GPUs, gloo host all-reduce"},
             "roofline": {"bound": "mfma", "kernel": dom,
                          "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
                          "traffic": tr[1]["traffic_bytes"] if tr else None,
@@ -783,15 +880,11 @@ def main():
                     "tflops": fvp_flops_per_row(widths) * n / fvp_s / 1e12},
             "alt_arithmetic": alt,
             "comm": comm,
-            "last_update": {k: last[k] for k in ("cg_iters", "k", "reverted", "kl_after", "surr_after")},
+            "last_update": {k: last[k] for k in LAST_UPDATE_KEYS},
             "cpu_baseline": None,
-        }
+        })
         if rehearsal and world > 1:
-            # ranks shared GPUs: not a measurement of N GPUs
-            out["rehearsal"] = True
-            out["n_gpus"] = min(ndev, local_world)
-            out["rehearsal_updates_per_s"] = value
-            out["value"] = None
+            mark_rehearsal(out, min(ndev, local_world))
             out["update_roofline"]["achieved_tflops"] = None
         if world == 1 and not args.no_cpu_baseline:
             threads, rep = host_cores()

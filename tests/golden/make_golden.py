@@ -251,12 +251,34 @@ def gen_rollout(U):
     _save("rollout.npz", **out)
 
 
+def fresh_inputs():
+    """Inputs of tests/test_oracle_golden.py::test_oracle_against_live_reference_utils (shared with that test)."""
+    rng = np.random.RandomState(123)
+    xs = [rng.uniform(-1, 1, n) for n in (1, 3, 57, 400)]
+    M = rng.standard_normal((30, 30))
+    A32 = (M @ M.T + 30 * np.eye(30)).astype(np.float32)
+    b = rng.standard_normal(30).astype(np.float32)
+    return xs, A32, b
+
+
+def gen_fresh(U):
+    """The reference's discount / conjugate_gradient on fresh_inputs(): outputs only (the test redraws the inputs)."""
+    xs, A32, b = fresh_inputs()
+    out = {f"discount_{len(x)}": np.asarray(U.discount(x, 0.97)) for x in xs}
+    out["cg_x"] = np.asarray(U.conjugate_gradient(lambda p: A32 @ p, b.copy(), 10, 1e-10))
+    _save("reference_fresh.npz", **out)
+
+
 def main(only=None):
     U = load_reference_utils()
     if only == "rollout":
         gen_rollout(U)
         return
+    if only == "fresh":
+        gen_fresh(U)
+        return
     gen_rollout(U)
+    gen_fresh(U)
     gen_discount(U)
     gen_cg(U)
     gen_linesearch(U)

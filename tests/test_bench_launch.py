@@ -144,6 +144,44 @@ def test_rank_digest_sees_every_bit():
     assert bench.rank_digest(v, dict(stats, rdotr=np.nextafter(1.0, 2.0))) != d0
 
 
+def test_dump_outputs_writes_npy_and_samples_over_budget(tmp_path):
+    """--dump-outputs: one .npy per output in its own dtype; over the byte budget, a fixed sample (same
+    elements in every run) of each array too large for its share, small arrays whole."""
+    import numpy as np
+    big = np.arange(1000, dtype=np.float32)
+    outs = {"theta": big, "stats": np.arange(11, dtype=np.float64)}
+    bench.dump_outputs(outs, str(tmp_path / "a"))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "theta.npy"), big)
+    assert np.load(tmp_path / "a" / "stats.npy").dtype == np.float64
+    for run in ("b", "c"):
+        bench.dump_outputs(outs, str(tmp_path / run), budget=800)
+    tb, tc = np.load(tmp_path / "b" / "theta.npy"), np.load(tmp_path / "c" / "theta.npy")
+    assert tb.dtype == np.float32 and tb.size == 100 and len(set(tb.tolist())) == 100
+    np.testing.assert_array_equal(tb, tc)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "stats.npy"), outs["stats"])
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 800 + 2 * 128   # the budget plus the two .npy headers
+
+
+def test_issued_arithmetic_without_a_profile_pass():
+    """The plain line's dtype label: f16x3 for every bench config under the default options (C1-C3 through
+    fused16.hip, C4 / C5 through the wide split row GEMMs), bf16x6 with the f16 split off, and bf16x6 for a
+    narrow shape outside fused16.hip's (three hidden layers), which issues no f16 split at all."""
+    from trpo_amd._lib import get_option, set_option
+    saved = get_option("split_f16")
+    try:
+        for c in bench.CONFIGS.values():
+            w = [c["obs"], *c["hidden"], c["A"]]
+            set_option("split_f16", 1)
+            assert bench.issued_arithmetic(w) == "f16x3", w
+            set_option("split_f16", 0)
+            assert bench.issued_arithmetic(w) == "bf16x6", w
+        set_option("split_f16", 1)
+        assert bench.issued_arithmetic([4, 64, 64, 64, 2]) == "bf16x6"
+    finally:
+        set_option("split_f16", saved)
+
+
 def test_fused_fvp_roofline_follows_the_issued_arithmetic():
     """The one-launch FVP is priced at the peak of the split it issues: f16 hi+lo (3 products) for fused16.hip's
     shapes with fused = 3, the exact bf16 split (6) for fused.hip; the fused policy gradient at 3, with its FLOPs

@@ -73,18 +73,26 @@ def test_update_tuple(name):
     np.testing.assert_allclose(r.losses_after, d["losses_after"], rtol=1e-9, atol=1e-14)
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not mounted (GPU box)")
 def test_oracle_against_live_reference_utils():
-    """Where the reference is mounted, re-run its numpy functions on fresh inputs."""
-    from oracle.ref_loader import load_reference_utils
-    U = load_reference_utils()
+    """The reference's numpy functions on fresh inputs: against their outputs recorded in reference_fresh.npz
+    (make_golden.py gen_fresh), and against the functions themselves where the reference is present."""
+    d = golden("reference_fresh.npz")
+    U = None
+    if reference_available():
+        from oracle.ref_loader import load_reference_utils
+        U = load_reference_utils()
     rng = np.random.RandomState(123)
     for n in (1, 3, 57, 400):
         x = rng.uniform(-1, 1, n)
-        np.testing.assert_array_equal(O.discount(x, 0.97), U.discount(x, 0.97))
+        np.testing.assert_array_equal(O.discount(x, 0.97), d[f"discount_{n}"])
+        if U is not None:
+            np.testing.assert_array_equal(O.discount(x, 0.97), U.discount(x, 0.97))
     M = rng.standard_normal((30, 30))
     A = M @ M.T + 30 * np.eye(30)
     b = rng.standard_normal(30).astype(np.float32)
     A32 = A.astype(np.float32)
     x1, _ = O.conjugate_gradient(lambda p: A32 @ p, b.copy(), 10, 1e-10)
-    np.testing.assert_array_equal(x1, U.conjugate_gradient(lambda p: A32 @ p, b.copy(), 10, 1e-10))
+    np.testing.assert_array_equal(x1, d["cg_x"])
+    assert x1.dtype == d["cg_x"].dtype
+    if U is not None:
+        np.testing.assert_array_equal(x1, U.conjugate_gradient(lambda p: A32 @ p, b.copy(), 10, 1e-10))

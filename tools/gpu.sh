@@ -48,7 +48,7 @@ case $CMD in
         c5) X="--steps 2 --warmup 1 --no-cpu-baseline --no-alt" ;;
         *)  X="--steps 20 --warmup 3 --no-cpu-baseline --no-alt" ;;
       esac
-      timeout -k 10 900 python -u bench.py --config $c $X --profile-out $OUT/events_$c.json "$@" \
+      timeout -k 10 900 python -u bench.py --full --config $c $X --profile-out $OUT/events_$c.json "$@" \
         > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
       summ $OUT/bench_$c.json $c
     done ;;
@@ -57,7 +57,7 @@ case $CMD in
     for r in $(seq 1 $R); do
       i=0
       for e in "$@"; do
-        timeout -k 10 300 env $e python -u bench.py --config $CFG --steps ${AB_STEPS:-5} --warmup 2 --no-cpu-baseline \
+        timeout -k 10 300 env $e python -u bench.py --full --config $CFG --steps ${AB_STEPS:-5} --warmup 2 --no-cpu-baseline \
           --no-alt ${AB_ARGS:-} --profile-out $OUT/ab_${i}_$r.prof.json > $OUT/ab_${i}_$r.json 2> $OUT/ab_${i}_$r.err \
           || { echo "variant [$e] failed"; tail -5 $OUT/ab_${i}_$r.err; exit 1; }
         summ $OUT/ab_${i}_$r.json "[$e] round $r" | tee -a $OUT/ab.txt
@@ -73,13 +73,13 @@ case $CMD in
   round)
     bash tools/gpu.sh tests $NAME && bash tools/gpu.sh smoke $NAME && bash tools/gpu.sh bench $NAME c4 c3 c2 c5 ;;
   rehearsal)   # 2 ranks sharing the one GPU (host all-reduce): the launcher and the per-rank digest check
-    timeout -k 10 600 python -u bench.py --gpus 2 --rehearsal --rows 400000 --steps 3 --warmup 1 --no-cpu-baseline \
+    timeout -k 10 600 python -u bench.py --full --gpus 2 --rehearsal --rows 400000 --steps 3 --warmup 1 --no-cpu-baseline \
       --no-alt > $OUT/bench_2rank_rehearsal.json 2> $OUT/bench_2rank_rehearsal.err || { tail -5 $OUT/bench_2rank_rehearsal.err; exit 1; }
     python -c "
 import json; d=json.loads(open('$OUT/bench_2rank_rehearsal.json').read().strip().splitlines()[-1])
 print('rehearsal', d['value'], d['comm'].get('transport'), d['comm'].get('ranks'), d['comm'].get('ranks_bitwise_equal'))" ;;
   rccl)   # every all-reduce through RCCL at world 1 (the N>1 code path minus the peers)
-    timeout -k 10 600 python -u bench.py --config c4 --steps 5 --warmup 2 --no-cpu-baseline --no-alt --rccl-world1 \
+    timeout -k 10 600 python -u bench.py --full --config c4 --steps 5 --warmup 2 --no-cpu-baseline --no-alt --rccl-world1 \
       > $OUT/bench_c4_rccl1.json 2> $OUT/bench_c4_rccl1.err || { tail -5 $OUT/bench_c4_rccl1.err; exit 1; }
     summ $OUT/bench_c4_rccl1.json c4-rccl1 ;;
   final)

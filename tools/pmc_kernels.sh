@@ -13,7 +13,7 @@ for GROUP in "GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_
              "SQ_INSTS_SALU SQ_INSTS_VMEM SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU_FP64"; do
   i=$((i+1))
   timeout -k 10 -s KILL 240 rocprofv3 --pmc $GROUP --output-format csv -d $OUT/pmc$i -o run -- \
-    python3 $ROOTD/bench.py --no-cpu-baseline --no-alt --steps 1 --warmup 0 --profile-steps 1 "$@" \
+    python3 $ROOTD/bench.py --full --no-cpu-baseline --no-alt --steps 1 --warmup 0 --profile-steps 1 "$@" \
     > $OUT/bench_pmc$i.log 2>&1 || { echo "pass $i failed rc=$?"; tail -3 $OUT/bench_pmc$i.log; }
 done
 echo done
