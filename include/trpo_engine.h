@@ -141,6 +141,29 @@ int trpo_compute_advantages(trpo_engine* e, double gamma, double* returns_out, d
  * runs on the current device for one process (n_global must equal n). */
 int trpo_standardize(trpo_engine* e, double* adv, int64_t n, int64_t n_global, float* adv32_out, int mem);
 
+/* ---- advantage estimator ---------------------------------------------------
+ * What trpo_compute_advantages (and trpo_update with compute_advantages = 1) standardises.
+ * TRPO_ADV_RETURNS, the default, is the reference's returns - baseline (trpo_inksci.py:102-105).
+ * TRPO_ADV_GAE is generalised advantage estimation, which the reference does not have; per path, float64,
+ * with end_t true on a path's last row, v = the baseline (0 when the feed has none):
+ *   vnext_t = end_t ? (tail_values ? tail_values[t] : 0) : v_{t+1}
+ *   delta_t = (r_t + gamma vnext_t) - v_t
+ *   A_t     = end_t ? delta_t : delta_t + gamma lambda A_{t+1}
+ *   R_t     = end_t ? r_t + gamma vnext_t : r_t + gamma R_{t+1}
+ * R stays the feed's returns (the VF's target, explained variance); A replaces returns - baseline. */
+#define TRPO_ADV_RETURNS 0
+#define TRPO_ADV_GAE 1
+/* kind = TRPO_ADV_RETURNS (lambda ignored) or TRPO_ADV_GAE with 0 <= lambda <= 1; engine state, kept
+ * across feeds.  kind and lambda are checked first, before the engine is touched. */
+int trpo_set_advantage_estimator(trpo_engine* e, int kind, double lambda);
+/* the estimator in force; either output may be NULL */
+int trpo_get_advantage_estimator(trpo_engine* e, int* kind, double* lambda);
+/* tail_values [n] f64 of the current feed: V(s_T) of paths that were cut off rather than terminated, read
+ * only at path-end rows; NULL clears them.  trpo_set_batch, trpo_set_rewards and trpo_rollout_to_batch
+ * clear them too.  Only TRPO_ADV_GAE uses them: computing advantages under TRPO_ADV_RETURNS while they
+ * are set fails with TRPO_ERR_STATE. */
+int trpo_set_tail_values(trpo_engine* e, const double* tail_values, int mem);
+
 /* ---- the graph outputs ---------------------------------------------------- */
 /* session.run(self.losses) -> [surr, kl, ent] at the current parameters (trpo_inksci.py:53,156) */
 int trpo_losses(trpo_engine* e, float out3[3]);
@@ -186,6 +209,12 @@ int trpo_device_count(int* out);
  * episode_starts may be NULL (one path). */
 int trpo_discount(const double* x, const uint8_t* episode_starts, int64_t n, double gamma,
                   double* out, int mem);
+/* GAE(lambda) (see TRPO_ADV_GAE) over a concatenation of paths on the current device: adv_out = A,
+ * returns_out = R.  values (V = 0), episode_starts (one path), tail_values (0) and either output may be
+ * NULL; n = 0 succeeds and writes nothing. */
+int trpo_gae(const double* rewards, const double* values, const uint8_t* episode_starts,
+             const double* tail_values, int64_t n, double gamma, double lambda, double* adv_out,
+             double* returns_out, int mem);
 
 /* ---- kernel-variant switches (for A/B measurements and variant parity tests) ----------
  * "split_mfma" (0 = f32 MFMA row GEMMs; 5 = the 256 x 256 split row-GEMM tile for outputs wider than

@@ -108,6 +108,16 @@ int main() {
   CHECK_ERR(trpo_standardize(nullptr, d.data(), 8, 16, nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
   CHECK_ERR(trpo_standardize(nullptr, d.data(), 9, 8, nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
   CHECK(trpo_standardize(nullptr, d.data(), 0, 0, nullptr, TRPO_MEM_HOST) == TRPO_OK);      // empty
+  CHECK_ERR(trpo_gae(nullptr, nullptr, nullptr, nullptr, 8, 0.95, 0.9, d.data(), nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_gae(d.data(), nullptr, nullptr, nullptr, -1, 0.95, 0.9, d.data(), nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_gae(d.data(), nullptr, nullptr, nullptr, 8, 0.95, 1.5, d.data(), nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK(trpo_gae(nullptr, nullptr, nullptr, nullptr, 0, 0.95, 0.9, nullptr, nullptr, TRPO_MEM_HOST) == TRPO_OK);   // n = 0
+  // the estimator's kind and lambda are checked before the engine
+  CHECK_ERR(trpo_set_advantage_estimator(nullptr, 7, 0.5), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_set_advantage_estimator(nullptr, TRPO_ADV_GAE, -0.1), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_set_advantage_estimator(nullptr, TRPO_ADV_GAE, 0.9), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_get_advantage_estimator(nullptr, nullptr, nullptr), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_set_tail_values(nullptr, d.data(), TRPO_MEM_HOST), TRPO_ERR_ARG);
   int64_t out[4];
   CHECK_ERR(trpo_cat_sample(nullptr, 4, 2, d.data(), out, TRPO_MEM_HOST), TRPO_ERR_ARG);
   CHECK(trpo_cat_sample(buf.data(), 0, 2, d.data(), out, TRPO_MEM_HOST) == TRPO_OK);

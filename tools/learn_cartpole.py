@@ -1,5 +1,6 @@
 """Run the reference's learn() loop (trpo_inksci.py:89-177) on CartPole-v0 on the GPU and print the
-reference's per-iteration statistics.  usage: python tools/learn_cartpole.py [iterations] [n_envs]"""
+reference's per-iteration statistics.  usage: python tools/learn_cartpole.py [iterations] [n_envs] [gae_lambda]
+(gae_lambda given: GAE(lambda) advantages instead of the reference's discount(rewards) - baseline)"""
 import os
 import sys
 import time
@@ -7,10 +8,12 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from trpo_amd import TRPOAgent  # noqa: E402
+from trpo_amd.agent import CONFIG  # noqa: E402
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 n_envs = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-agent = TRPOAgent(4, 2, hidden=(64,), max_rows=8192)
+gae_lambda = float(sys.argv[3]) if len(sys.argv) > 3 else None
+agent = TRPOAgent(4, 2, hidden=(64,), max_rows=8192, config={**CONFIG, "gae_lambda": gae_lambda})
 t0 = time.time()
 hist = agent.learn(max_iterations=iters, n_envs=n_envs, seed=1)
 dt = time.time() - t0

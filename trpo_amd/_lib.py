@@ -19,6 +19,8 @@ MEM_DEVICE = 1
 
 VEC_THETA, VEC_THETA_PREV, VEC_G, VEC_STEPDIR, VEC_FULLSTEP, VEC_THETA_LS = range(6)
 
+ADV_RETURNS, ADV_GAE = 0, 1
+
 
 class UpdateParams(ctypes.Structure):
     _fields_ = [("cg_iters", c_int), ("residual_tol", c_float), ("cg_damping", c_float),
@@ -76,6 +78,9 @@ SIGNATURES = {
     "trpo_set_rewards": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "trpo_compute_advantages": (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_int]),
     "trpo_standardize": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int]),
+    "trpo_set_advantage_estimator": (c_int, [c_void_p, c_int, c_double]),
+    "trpo_get_advantage_estimator": (c_int, [c_void_p, POINTER(c_int), POINTER(c_double)]),
+    "trpo_set_tail_values": (c_int, [c_void_p, c_void_p, c_int]),
     "trpo_losses": (c_int, [c_void_p, POINTER(c_float)]),
     "trpo_eval_losses": (c_int, [c_void_p, c_void_p, POINTER(c_float), c_int]),
     "trpo_action_dist": (c_int, [c_void_p, c_void_p, c_int]),
@@ -89,6 +94,8 @@ SIGNATURES = {
     "trpo_update": (c_int, [c_void_p, POINTER(UpdateParams), POINTER(UpdateStats)]),
     "trpo_device_count": (c_int, [POINTER(c_int)]),
     "trpo_discount": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p, c_int]),
+    "trpo_gae": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p,
+                         c_int]),
     "trpo_set_option": (c_int, [c_char_p, c_int]),
     "trpo_get_option": (c_int, [c_char_p, POINTER(c_int)]),
     "trpo_profile_enable": (c_int, [c_void_p, c_int]),

@@ -18,6 +18,11 @@ Two ways to run one policy update, both on the GPU:
 For the update methods, paths come in as the reference's dicts
 (``utils.py:36-39``) with an optional ``"baseline"`` entry (zeros otherwise, as
 ``VF.predict`` returns before its first fit, ``utils.py:88-89``).
+
+``config["gae_lambda"]`` (not in the reference) switches the advantages of all three
+from ``discount(rewards) - baseline`` to GAE(lambda); paths may then carry a
+``"tail_value"`` scalar, V(s_T) of a path that was cut off rather than terminated.
+learn() keeps CartPole-v0's time limit as a termination, as the reference does.
 """
 from __future__ import annotations
 
@@ -34,6 +39,8 @@ from .utils import (EngineLoss, GetFlat, KLFirstFixedGVP, SetFromFlat, Surrogate
 
 CONFIG = {"max_steps": 1000, "episodes_per_roll": 1000, "gamma": 0.95, "cg_damping": 0.1,
           "max_kl": 0.01}   # trpo_inksci.py:17
+# An optional "gae_lambda" key (absent or None here: the reference's discount(rewards) - baseline) selects
+# GAE(lambda) advantages on the engine, with the VF's baseline as V.
 
 
 class Session:
@@ -86,6 +93,14 @@ def paths_to_batch(paths: List[Dict]) -> Dict[str, np.ndarray]:
                                     for p in paths]),
         "starts": np.concatenate(starts),
     }
+    if any("tail_value" in p for p in paths):
+        # V(s_T) of a path that was cut off rather than terminated (GAE's bootstrap), at its last row
+        tails = []
+        for p in paths:
+            t = np.zeros(len(p["rewards"]), np.float64)
+            t[-1] = float(p.get("tail_value", 0.0))
+            tails.append(t)
+        out["tail_values"] = np.concatenate(tails)
     return out
 
 
@@ -111,6 +126,8 @@ class TRPOAgent:
         self.end_count = 0                                       # :29
         self.vf = VF(self.session, max_rows=max_rows, device=device)   # :73
         self.rank, self.world, self.group = 0, 1, None
+        if self.config.get("gae_lambda") is not None:
+            self.engine.set_advantage_estimator("gae", self.config["gae_lambda"])
 
     def set_ranks(self, rank: int, world: int, group=None, host_allreduce: bool = False):
         """Run learn() as one of `world` ranks (one process per GPU, torch.distributed initialised by the
@@ -161,6 +178,8 @@ class TRPOAgent:
         self.engine.set_batch(b["state"], b["action"], b.get("advant"), b["action_dist"], n_global)
         if "rewards" in b:
             self.engine.set_rewards(b["rewards"], b["starts"], b.get("baseline"))
+            if b.get("tail_values") is not None:
+                self.engine.set_tail_values(b["tail_values"])
         return b
 
     def update(self, paths_or_batch, n_global: Optional[int] = None, cg_iters: int = 10,

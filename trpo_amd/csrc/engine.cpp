@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -72,6 +73,12 @@ struct trpo_engine {
   double *rewards = nullptr, *returns = nullptr, *adv64 = nullptr, *baseline = nullptr;
   uint8_t* starts = nullptr;
   bool have_baseline = false, have_rewards = false, have_returns = false;
+  // advantage estimator (trpo_set_advantage_estimator) and the feed's optional tail values (GAE's V(s_T) of
+  // cut-off paths, allocated on first use)
+  int adv_kind = TRPO_ADV_RETURNS;
+  double adv_lambda = 1.0;
+  double* tail = nullptr;
+  bool have_tail = false;
   double* ev_tmp = nullptr;   // explained_variance scratch
   std::vector<float*> H, D, E, RH, RD;   // indexed as in DESIGN.md
   float *Pm = nullptr, *DSL = nullptr;
@@ -438,7 +445,7 @@ struct trpo_engine {
     part3 = dalloc<double>(kRedBlocks * 3);
     local3 = dalloc<double>(4);
     dscal = dalloc<double>(8);
-    scan_ws = dalloc<uint8_t>(discount_workspace_bytes(cap));
+    scan_ws = dalloc<uint8_t>(std::max(discount_workspace_bytes(cap), gae_workspace_bytes(cap)));
     sc = dalloc<UpdScalars>(1);
     fl = dalloc<CGFlags>(1);
     cg_ticket = dalloc<unsigned>(1);
@@ -1778,10 +1785,26 @@ struct trpo_engine {
     reduce_losses(1, nullptr);
   }
 
+  // tail values belong to GAE; the returns estimator would silently drop them
+  void check_estimator_state() const {
+    if (have_tail && adv_kind == TRPO_ADV_RETURNS)
+      throw std::runtime_error(
+          "tail values are set but the advantage estimator is TRPO_ADV_RETURNS: select TRPO_ADV_GAE or clear them");
+  }
+
   void compute_advantages(double gamma) {
     REQUIRE(have_rewards, "no rewards: call trpo_set_rewards first");
-    launch_discount(rewards, starts, n, gamma, returns, scan_ws, stream);
-    launch_adv_center_partials(returns, have_baseline ? baseline : nullptr, adv64, n, partA, stream);
+    check_estimator_state();
+    if (adv_kind == TRPO_ADV_GAE) {
+      // one scan writes the returns and the raw advantages; the standardisation then runs in place, the
+      // launches of standardize()
+      launch_gae(rewards, have_baseline ? baseline : nullptr, starts, have_tail ? tail : nullptr, n, gamma,
+                 adv_lambda, adv64, returns, scan_ws, stream);
+      launch_adv_center_partials(adv64, nullptr, adv64, n, partA, stream);
+    } else {
+      launch_discount(rewards, starts, n, gamma, returns, scan_ws, stream);
+      launch_adv_center_partials(returns, have_baseline ? baseline : nullptr, adv64, n, partA, stream);
+    }
     launch_sum_finish(partA, dscal, stream);
     allreduce_f64(dscal, 1);
     const double inv_n = 1.0 / (double)n_global;
@@ -1872,12 +1895,17 @@ struct trpo_engine {
     const void* host_ar;
     int rank, world;
     int cg_iters, adv, baseline;
+    int adv_kind, tail;   // the estimator's kind and whether the feed has tail values: they pick the captured scan
     int x_planes;   // X's planes hold the current batch: the captured plane kernels read them (set_batch
                     // writes them outside the graph, so a replay must not outlive a change of this flag)
     float tol, damping;
     double gamma;
+    double lambda;   // GAE's lambda is a kernel argument of the captured scan
     Options opt;
   };
+  static_assert(offsetof(GraphKey, opt) ==
+                    2 * sizeof(int64_t) + 2 * sizeof(void*) + 8 * sizeof(int) + 2 * sizeof(float) + 2 * sizeof(double),
+                "GraphKey is compared with memcmp: keep it free of padding");
   GraphKey graph_key(const trpo_update_params& prm) const {
     GraphKey k;
     std::memset(&k, 0, sizeof k);
@@ -1890,6 +1918,9 @@ struct trpo_engine {
     k.cg_iters = prm.cg_iters;
     k.adv = prm.compute_advantages != 0;
     k.baseline = have_baseline;
+    k.adv_kind = adv_kind;
+    k.tail = have_tail ? 1 : 0;
+    k.lambda = adv_lambda;
     k.x_planes = x_planes ? 1 : 0;
     k.tol = prm.residual_tol;
     k.damping = prm.cg_damping;
@@ -1983,6 +2014,7 @@ struct trpo_engine {
     require_batch();
     REQUIRE(prm.cg_iters >= 0 && prm.cg_iters <= kMaxCG, "cg_iters out of range");
     REQUIRE(!prm.compute_advantages || have_rewards, "no rewards: call trpo_set_rewards first");
+    if (prm.compute_advantages) check_estimator_state();   // before any capture begins
     // max_kl goes to the scalar block before shs_finish reads it (no prefix kernel writes it)
     HIPCHECK(hipMemcpyAsync(&sc->max_kl, &prm.max_kl, sizeof(double), hipMemcpyHostToDevice, stream));
     run_prefix(prm);
@@ -2210,6 +2242,7 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
     e->prepared = false;
     e->have_rewards = false;
     e->have_returns = false;
+    e->have_tail = false;
   });
 }
 
@@ -2225,6 +2258,40 @@ int trpo_set_rewards(trpo_engine* e, const double* rewards, const uint8_t* start
     if (baseline) e->copy_in(e->baseline, baseline, (size_t)e->n * sizeof(double), mem);
     e->have_rewards = true;
     e->have_returns = false;
+    e->have_tail = false;
+  });
+}
+
+int trpo_set_advantage_estimator(trpo_engine* e, int kind, double lambda) {
+  return guarded([&] {
+    REQUIRE(kind == TRPO_ADV_RETURNS || kind == TRPO_ADV_GAE, "kind must be TRPO_ADV_RETURNS or TRPO_ADV_GAE");
+    REQUIRE(kind != TRPO_ADV_GAE || (lambda >= 0.0 && lambda <= 1.0), "lambda must be in [0, 1]");   // NaN fails
+    REQUIRE(e, "engine is NULL");
+    e->adv_kind = kind;
+    e->adv_lambda = kind == TRPO_ADV_GAE ? lambda : 1.0;
+  });
+}
+
+int trpo_get_advantage_estimator(trpo_engine* e, int* kind, double* lambda) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    if (kind) *kind = e->adv_kind;
+    if (lambda) *lambda = e->adv_lambda;
+  });
+}
+
+int trpo_set_tail_values(trpo_engine* e, const double* tail_values, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    if (!tail_values) {
+      e->have_tail = false;
+      return;
+    }
+    e->require_batch();
+    e->use();
+    if (!e->tail) e->tail = e->dalloc<double>(e->cap);
+    e->copy_in(e->tail, tail_values, (size_t)e->n * sizeof(double), mem);
+    e->have_tail = true;
   });
 }
 
@@ -2603,6 +2670,7 @@ int trpo_rollout_to_batch(trpo_engine* e, int64_t n_global) {
     e->have_rewards = true;
     e->have_returns = false;
     e->have_baseline = false;
+    e->have_tail = false;
     HIPCHECK(hipStreamSynchronize(e->stream));
   });
 }
@@ -2794,6 +2862,53 @@ int trpo_discount(const double* x, const uint8_t* starts, int64_t n, double gamm
     (void)hipFree(ds);
     if (dx) (void)hipFree(dx);
     if (dy) (void)hipFree(dy);
+  });
+}
+
+int trpo_gae(const double* rewards, const double* values, const uint8_t* starts, const double* tail_values,
+             int64_t n, double gamma, double lambda, double* adv_out, double* returns_out, int mem) {
+  return guarded([&] {
+    REQUIRE(n >= 0, "n < 0");
+    REQUIRE(lambda >= 0.0 && lambda <= 1.0, "lambda must be in [0, 1]");
+    if (n == 0) return;
+    REQUIRE(rewards, "rewards is NULL");
+    const bool dev = mem == TRPO_MEM_DEVICE;
+    hipStream_t s = nullptr;
+    std::vector<void*> tmps;
+    auto alloc = [&](size_t bytes) {
+      void* ptr = nullptr;
+      HIPCHECK(hipMalloc(&ptr, std::max<size_t>(bytes, 16)));
+      tmps.push_back(ptr);
+      return ptr;
+    };
+    // a host input becomes a device copy; a device input is read in place
+    auto in = [&](const void* src, size_t bytes) -> const void* {
+      if (!src || dev) return src;
+      void* d = alloc(bytes);
+      HIPCHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+      return d;
+    };
+    try {
+      const size_t nd = (size_t)n * sizeof(double);
+      const double* dr = static_cast<const double*>(in(rewards, nd));
+      const double* dv = static_cast<const double*>(in(values, nd));
+      const uint8_t* ds = static_cast<const uint8_t*>(in(starts, (size_t)n));
+      const double* dt = static_cast<const double*>(in(tail_values, nd));
+      double* da = adv_out && !dev ? static_cast<double*>(alloc(nd)) : adv_out;
+      double* dret = returns_out && !dev ? static_cast<double*>(alloc(nd)) : returns_out;
+      void* ws = alloc(gae_workspace_bytes(n));
+      launch_gae(dr, dv, ds, dt, n, gamma, lambda, da, dret, ws, s);
+      check_launch();
+      HIPCHECK(hipDeviceSynchronize());
+      if (!dev) {
+        if (adv_out) HIPCHECK(hipMemcpy(adv_out, da, nd, hipMemcpyDeviceToHost));
+        if (returns_out) HIPCHECK(hipMemcpy(returns_out, dret, nd, hipMemcpyDeviceToHost));
+      }
+    } catch (...) {
+      for (void* ptr : tmps) (void)hipFree(ptr);
+      throw;
+    }
+    for (void* ptr : tmps) (void)hipFree(ptr);
   });
 }
 

@@ -351,6 +351,17 @@ void launch_adv_sq_partials(const double* adv, int64_t n, const double* global_s
 void launch_adv_normalize(double* adv, float* adv32, int64_t n, const double* global_sum,
                           const double* global_sq, double inv_n, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// GAE(lambda) two-channel scan (gae.hip)
+// ---------------------------------------------------------------------------
+// returns[t] = r[t] + gamma*returns[t+1], adv[t] = delta[t] + gamma*lambda*adv[t+1] within episodes, with
+// delta[t] = (r[t] + gamma*v[t+1]) - v[t]; at a path's last row v[t+1] is tail_values[t] (0 when NULL) and
+// both carries are cut.  values, starts (one path), tail_values and either output may be NULL.
+size_t gae_workspace_bytes(int64_t n);
+void launch_gae(const double* rewards, const double* values, const uint8_t* starts, const double* tail_values,
+                int64_t n, double gamma, double lambda, double* adv, double* returns, void* workspace,
+                hipStream_t s);
+
 }  // namespace trpo
 
 namespace trpo {

@@ -18,6 +18,8 @@ from ._lib import MEM_DEVICE, MEM_HOST, check, lib
 
 __all__ = ["Engine", "UpdateParams"]
 
+_ADV_KINDS = {"returns": _lib.ADV_RETURNS, "gae": _lib.ADV_GAE}
+
 
 def _is_torch(x) -> bool:
     mod = type(x).__module__
@@ -200,6 +202,29 @@ class Engine:
         """The VF.predict baselines of the current feed (trpo_inksci.py:103), f64 [n]."""
         b = _Arg(baseline, np.float64, (self.n,))
         check(lib.trpo_set_baseline(self._h, b.ptr, b.mem), "trpo_set_baseline")
+
+    def set_advantage_estimator(self, kind: str = "returns", lam: float = 1.0):
+        """What compute_advantages / update(compute_advantages=True) standardise: "returns" (the
+        reference's returns - baseline, the default) or "gae" (GAE(lambda), 0 <= lam <= 1, with the feed's
+        baseline as V).  Engine state: it holds across feeds until set again."""
+        if kind not in _ADV_KINDS:
+            raise ValueError(f"set_advantage_estimator: kind must be one of {sorted(_ADV_KINDS)}, got {kind!r}")
+        check(lib.trpo_set_advantage_estimator(self._h, _ADV_KINDS[kind], float(lam)),
+              "trpo_set_advantage_estimator")
+
+    @property
+    def advantage_estimator(self):
+        """(kind, lam) in force: ("returns", 1.0) unless set_advantage_estimator chose otherwise."""
+        kind, lam = ctypes.c_int(0), ctypes.c_double(0.0)
+        check(lib.trpo_get_advantage_estimator(self._h, ctypes.byref(kind), ctypes.byref(lam)),
+              "trpo_get_advantage_estimator")
+        return {v: k for k, v in _ADV_KINDS.items()}[kind.value], lam.value
+
+    def set_tail_values(self, tail_values):
+        """V(s_T) of the current feed's cut-off paths for GAE, f64 [n], read only at path-end rows; None
+        clears them (as set_batch, set_rewards and rollout_to_batch do)."""
+        t = _Arg(tail_values, np.float64, (self.n,)) if tail_values is not None else _Arg(None, np.float64)
+        check(lib.trpo_set_tail_values(self._h, t.ptr, t.mem), "trpo_set_tail_values")
 
     def feed_view(self) -> "_lib.FeedView":
         """Device pointers into the current feed (synchronises the engine stream)."""
@@ -445,6 +470,32 @@ def discount_device(x, gamma: float, episode_starts=None) -> np.ndarray:
         oa = _Arg(out, np.float64, writable=True)
     check(lib.trpo_discount(xa.ptr, st.ptr, n, float(gamma), oa.ptr, xa.mem), "trpo_discount")
     return out
+
+
+def gae_device(rewards, values, gamma: float, lam: float, episode_starts=None, tail_values=None):
+    """Engine-free GAE(lambda) on the current GPU (include/trpo_engine.h, TRPO_ADV_GAE): returns
+    (advantages, returns), f64 [n].  values=None is V = 0, episode_starts=None one path, tail_values=None
+    zero bootstrap values.  Host arrays or device tensors (all of one kind)."""
+    ra = _Arg(rewards, np.float64)
+    dev = ra.mem == MEM_DEVICE
+    n = int(ra.obj.numel()) if _is_torch(ra.obj) else int(ra.obj.shape[0])
+    opt = lambda x: _Arg(x, np.float64, (n,)) if x is not None else _Arg(None, np.float64)   # noqa: E731
+    va, ta = opt(values), opt(tail_values)
+    st = _Arg(None, np.uint8) if episode_starts is None else _Arg(
+        np.asarray(episode_starts).astype(np.uint8) if not _is_torch(episode_starts) else episode_starts,
+        np.uint8, (n,))
+    if any(x.ptr is not None and x.mem != ra.mem for x in (va, ta, st)):
+        raise ValueError("gae_device: pass all host arrays or all device tensors")
+    if dev:
+        import torch
+        adv = torch.empty(n, dtype=torch.float64, device=ra.obj.device)
+        ret = torch.empty(n, dtype=torch.float64, device=ra.obj.device)
+    else:
+        adv, ret = np.empty(n, np.float64), np.empty(n, np.float64)
+    aa, rr = _Arg(adv, np.float64, writable=True), _Arg(ret, np.float64, writable=True)
+    check(lib.trpo_gae(ra.ptr, va.ptr, st.ptr, ta.ptr, n, float(gamma), float(lam), aa.ptr, rr.ptr, ra.mem),
+          "trpo_gae")
+    return adv, ret
 
 
 def _standardize(handle, adv, n_global, adv32_out):

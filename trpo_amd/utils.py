@@ -24,6 +24,9 @@ cat_sample      :95-105       ``cat_sample(prob_nk)``                    device 
 dict2           :203-206      same                                       -
 ============================  =========================================  ===============================
 
+Not in the reference: ``gae(rewards, values, gamma, lam, ...)``, GAE(lambda) advantages by a device
+segmented scan (f64), beside ``discount``.
+
 ``session`` here is a :class:`trpo_amd.agent.Session` (or anything with an
 ``engine`` attribute, or an :class:`~trpo_amd.engine.Engine`).
 """
@@ -31,10 +34,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import Engine, cat_sample_device, cg_callback, discount_device
+from .engine import Engine, cat_sample_device, cg_callback, discount_device, gae_device
 from .vf import VF  # noqa: F401  (utils.py:48-92)
 
-__all__ = ["discount", "conjugate_gradient", "linesearch", "flatgrad", "GetFlat", "SetFromFlat",
+__all__ = ["discount", "gae", "conjugate_gradient", "linesearch", "flatgrad", "GetFlat", "SetFromFlat",
            "var_shape", "numel", "explained_variance", "FisherVectorProduct", "SurrogateLoss", "VF",
            "cat_sample", "rollout", "dict2"]
 
@@ -60,6 +63,14 @@ def discount(x, gamma):
     for c in range(flat.shape[1]):
         out[:, c] = discount_device(np.ascontiguousarray(flat[:, c]), gamma)
     return out.reshape(x.shape)
+
+
+def gae(rewards, values, gamma, lam, episode_starts=None, tail_values=None):
+    """GAE(lambda) advantages of a concatenation of paths on the GPU (not in the reference, whose only
+    estimator is discount(rewards, gamma) - baseline): A_t = delta_t + gamma*lam*A_{t+1} with
+    delta_t = (r_t + gamma*V_{t+1}) - V_t, cut at path ends, where V_{t+1} is tail_values[t] (0 when None).
+    values=None is V = 0.  Host arrays or device tensors; ``engine.gae_device`` also gives the returns."""
+    return gae_device(rewards, values, gamma, lam, episode_starts, tail_values)[0]
 
 
 # ---------------------------------------------------------------------------- utils.py:108-116
