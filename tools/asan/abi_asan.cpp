@@ -1,5 +1,5 @@
 // Host AddressSanitizer driver for the C-ABI ("host side: ASan on the C++ runtime
-// build").  Built by `make -C trpo_amd/csrc asan` (engine.cpp / vf.cpp host code instrumented with
+// build").  Built by `make -C trpo_amd/csrc asan` (engine.cpp / vf.cpp / standalone.cpp host code instrumented with
 // -fsanitize=address; device objects unchanged) and run by tests/test_asan.py on a CPU-only host:
 // every entry point's argument validation, error reporting and cleanup of a partially
 // initialised engine, with no GPU present.  Exit code 0 = all checks passed, ASan clean.

@@ -123,8 +123,7 @@ int main(int argc, char** argv) {
     WGradArgs w{};
     w.rows = (int)M; w.Ma = K; w.Nb = N; w.Mpad = K; w.Npad = N; w.nseg = 2;
     w.seg[0] = WSeg{RH, RH2, K, N}; w.seg[1] = WSeg{H, E, K, N}; w.colsum_seg = 1;
-    w.splits = (int)((M + rps - 1) / rps); w.rows_per_split = (int)rps; w.slab = slab;
-    w.slab_stride = N * K + N; w.off_w = 0; w.off_b = N * K;
+    w.dst = SlabDst{(int)((M + rps - 1) / rps), (int)rps, slab, N * K + N, 0, N * K};
     for (int mode : {0, 1, 2, 3, 101, 102, 103}) {
       g_options.split_wg = mode % 100;
       w.f16 = mode / 100;

@@ -1,5 +1,5 @@
-// Error plumbing shared by the C-ABI translation units (engine.cpp, vf.cpp, rollout.cpp):
-// every exported entry runs its body under guarded(), which maps the exception
+// Error plumbing and host/device staging shared by the C-ABI translation units (engine.cpp, vf.cpp,
+// standalone.cpp): every exported entry runs its body under guarded(), which maps the exception
 // type to the TRPO_ERR_* code and keeps the message for trpo_last_error().
 #pragma once
 #include "../../include/trpo_engine.h"
@@ -7,8 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace trpo_abi {
 
@@ -79,5 +81,60 @@ inline void copy_out(void* dst, const void* src, size_t bytes, int mem, hipStrea
                           s));
   HIPCHECK(hipStreamSynchronize(s));
 }
+
+// Device staging of one C-ABI call's caller arrays (mem = TRPO_MEM_*) on stream `s`: a device array is used in
+// place, a host array gets a device temporary (inputs copied in at once, outputs copied back by fetch()); NULL
+// stays NULL.  The destructor frees every temporary, so nothing leaks when a launch or a copy throws.
+class Staging {
+ public:
+  Staging(int mem, hipStream_t s) : host_(mem != TRPO_MEM_DEVICE), s_(s) {}
+  Staging(const Staging&) = delete;
+  Staging& operator=(const Staging&) = delete;
+  ~Staging() {
+    for (void* p : bufs_) (void)hipFree(p);
+  }
+  template <class T>
+  T* tmp(size_t count) {   // a device temporary (uninitialised)
+    void* p = nullptr;
+    HIPCHECK(hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)));
+    bufs_.push_back(p);
+    return static_cast<T*>(p);
+  }
+  template <class T>
+  const T* in(const T* src, size_t count) {
+    if (!src || !host_) return src;
+    T* d = tmp<T>(count);
+    copy_in(d, src, count * sizeof(T), TRPO_MEM_HOST, s_);
+    return d;
+  }
+  template <class T>
+  T* out(T* dst, size_t count) {
+    if (!dst || !host_) return dst;
+    T* d = tmp<T>(count);
+    outs_.push_back(Out{dst, d, count * sizeof(T)});
+    return d;
+  }
+  template <class T>
+  T* inout(T* p, size_t count) {   // read and written in place
+    T* d = out(p, count);
+    if (d != p) copy_in(d, p, count * sizeof(T), TRPO_MEM_HOST, s_);
+    return d;
+  }
+  // the host outputs, once the work is enqueued on the stream; each copy waits for the stream
+  void fetch() {
+    for (const Out& o : outs_) copy_out(o.host, o.dev, o.bytes, TRPO_MEM_HOST, s_);
+  }
+
+ private:
+  struct Out {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  };
+  bool host_;
+  hipStream_t s_;
+  std::vector<void*> bufs_;
+  std::vector<Out> outs_;
+};
 
 }  // namespace trpo_abi

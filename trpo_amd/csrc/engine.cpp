@@ -65,14 +65,13 @@ struct trpo_engine {
   // bf16 (hi, mid, lo) planes of the packed matrices for the split-bf16 row GEMM:
   // [part][3][Npad][r16(K)], part 0 = W half, 1 = V half (WF3t: W half only)
   std::vector<uint16_t*> WF3, WB3, WFt3;
-  bool w3_valid = false;   // W halves of WF3/WB3 match WF/WB
   float* X = nullptr;
   float* stage = nullptr;   // staging for host inputs / compact outputs: cap rows of max(pad4(obs), pad4(A), 2) floats
   int* act = nullptr;
   float *adv32 = nullptr, *old = nullptr;
   double *rewards = nullptr, *returns = nullptr, *adv64 = nullptr, *baseline = nullptr;
   uint8_t* starts = nullptr;
-  bool have_baseline = false, have_rewards = false, have_returns = false;
+  bool have_baseline = false, have_rewards = false;
   // advantage estimator (trpo_set_advantage_estimator) and the feed's optional tail values (GAE's V(s_T) of
   // cut-off paths, allocated on first use)
   int adv_kind = TRPO_ADV_RETURNS;
@@ -94,7 +93,56 @@ struct trpo_engine {
   int* dbad = nullptr;
   UpdScalars* hsc = nullptr;   // pinned host mirror
 
-  bool prepared = false;
+  // What the device buffers hold beyond their raw contents.  Every host flag that update_prefix() leaves behind
+  // lives here: a replayed hipGraph runs no host code, so run_prefix() copies this record after the capture
+  // (upd_state = cache) and puts it back after every replay (cache = upd_state).
+  struct CacheState {
+    bool prepared = false;        // prepare()'s outputs match theta, the batch and the advantages
+    bool w3_valid = false;        // W halves of WF3/WB3 match WF/WB
+    bool chain_w_valid = false;   // theta parts of the chain images match theta
+    bool f16_w_valid = false;     // theta parts of the f16 images match theta
+    bool have_returns = false;    // `returns` holds the current rewards' returns
+    bool prep_e_top = true;       // prepare() wrote E_{L-2}
+    bool prep_fused16 = false;    // prepare() took the fused16 branch (D_1 / E_1 / E_0 and the pg slabs from bwd_pg)
+    // the prepare pass also produced the policy gradient's DS_{L-2} (hbwd.hip, in RD[L-2]) and its head-layer block
+    // of the slabs
+    bool ds_ready = false;
+    // fused16.hip's prepare launch also left the policy gradient's blocks in the first pg_grid slabs
+    bool pg_ready = false;
+    int pg_grid = 0;
+    bool d1_plane = false;   // D1h holds the current D_1 (row stride d1_mpad = round256(n))
+    bool d1_tiled = false;   // ... with one scale per 32-row tile (eD1t, hbwd.hip) instead of pl_e[1]
+    int d1_mpad = 0;
+
+    // theta changed: what prepare() derived from it is stale
+    void theta_changed() { prepared = false; }
+    // the batch changed: prepare()'s outputs and the returns belong to the old rows
+    void batch_changed() { prepared = have_returns = false; }
+    // new rewards: the returns are the old ones'
+    void rewards_changed() { have_returns = false; }
+    // the advantages (and with them the returns) were recomputed: the prepare head's DS_L and losses are stale
+    void advantages_computed() {
+      prepared = false;
+      have_returns = true;
+    }
+    // prepare() starts over from freshly packed weights: their planes and images are rebuilt on demand, nothing
+    // of an earlier pass is left for the policy gradient or the FVP, and this pass serves the given path
+    void prepare_begins(bool e_top, bool fused16) {
+      w3_valid = chain_w_valid = f16_w_valid = false;
+      ds_ready = pg_ready = d1_plane = d1_tiled = false;
+      prep_e_top = e_top;
+      prep_fused16 = fused16;
+    }
+    // a launch wrote the slabs: the prepare pass's policy-gradient blocks are gone, except the head-layer block
+    // when the writer is the policy gradient's own lower layers (keeps_pg_head)
+    void slabs_written(bool keeps_pg_head = false) {
+      pg_ready = false;
+      if (!keeps_pg_head) ds_ready = false;
+    }
+    // a launch wrote RD: DS_{L-2} lived in RD[L-2]
+    void rd_written() { ds_ready = false; }
+  } cache;
+
   // f16 split GEMMs: running max |operand| slots (float bits) that set the power-of-two scales,
   // grouped by kind, kMaxLayers slots per group (see am_*)
   bool f16 = false;
@@ -119,20 +167,11 @@ struct trpo_engine {
   // W / V weight planes, re-blocked from WF3 / WFt3 before each use
   uint16_t *Xh = nullptr, *Xl = nullptr, *W0b = nullptr, *V0b = nullptr;
   int* pl_e = nullptr;   // scale exponents published by the plane producers: [0] = X, [1] = D_1
-  // D_1's f16 hi plane (k-blocked like Xh, stride d1_mpad = round256(n)), written by prepare() for the fused
-  // R-backward's one-product D_1 V_1^T segment (rbwd0.hip)
+  // D_1's f16 hi plane (k-blocked like Xh, stride cache.d1_mpad), written by prepare() for the fused
+  // R-backward's one-product D_1 V_1^T segment (rbwd0.hip), and its per-tile scale exponents
   uint16_t* D1h = nullptr;
-  int d1_mpad = 0, d1_ldp = 0;
-  bool d1_plane = false;   // D1h holds the current D_1
-  bool d1_tiled = false;   // ... with one scale per 32-row tile (eD1t, hbwd.hip) instead of pl_e[1]
+  int d1_ldp = 0;
   int* eD1t = nullptr;
-  // the prepare pass also produced the policy gradient's DS_{L-2} (hbwd.hip, in RD[L-2]); any launch that
-  // writes RD clears it
-  bool ds_ready = false;
-  // fused16.hip's prepare launch also left the policy gradient's blocks in the first pg_grid slabs; any slab writer
-  // clears it
-  bool pg_ready = false;
-  int pg_grid = 0;
   bool use_hbwd2() const {
     // a hidden layer below the head layer, wider than 128 (one thread per column: at 64 columns three
     // quarters of its lanes idle, and C3 ran 3 % slower than on the row GEMMs); E_{L-2} is written too
@@ -169,11 +208,10 @@ struct trpo_engine {
   // whether the FVP path reads E_{L-2} (the plain tanh'' term under the last hidden layer): every path
   // but the fused tail, which recomputes it (tail.hip)
   bool e_top_needed() const { return L < 2 || !use_tail() || use_fused() || use_chain(); }
-  bool prep_e_top = true;    // prepare() wrote E_{L-2}
-  bool prep_fused16 = false; // prepare() took the fused16 branch (D_1 / E_1 / E_0 and the pg slabs from bwd_pg)
   // prepare()'s outputs belong to the other kernel path when option fused / split_f16 changed after it ran
   void reprepare_if_path_changed() {
-    if (prepared && ((e_top_needed() && !prep_e_top) || prep_fused16 != use_fused16())) prepared = false;
+    if (cache.prepared && ((e_top_needed() && !cache.prep_e_top) || cache.prep_fused16 != use_fused16()))
+      cache.prepared = false;
   }
 
   // fused FVP chain (chain.hip): weight images in consumption order + chunk table
@@ -181,7 +219,6 @@ struct trpo_engine {
   uint16_t* chain_img = nullptr;
   int* chain_tab = nullptr;
   int chain_nchunks = 0;
-  bool chain_w_valid = false;   // theta parts of the images match theta
   ChainImgArgs chain_jobs{};
   // auto (option 1) takes the chain up to 8 register tiles (hidden widths <= 128), where it
   // beats the per-layer row GEMMs; at 16 tiles its per-128-state weight re-streaming
@@ -197,7 +234,6 @@ struct trpo_engine {
   bool f16_v_img_ready = false;   // cg(): the V images of the next fvp_fused16 were built by the CG step launch
   unsigned* cg_ticket = nullptr;  // cg_step_slabs_kernel's arrival ticket (zero between launches)
   int f16_nchunks = 0;
-  bool f16_w_valid = false;     // theta parts of the f16 images match theta
   ChainImgArgs f16_jobs{};
   // the line-search loss forward's images (W_0 | W_1 | W_2 of the trial vector, fwd_loss16)
   uint16_t* f16_limg = nullptr;
@@ -213,12 +249,12 @@ struct trpo_engine {
   // the R-forward through layers 0 and 1 in one launch: X's planes, the fused tail (RZ2 is its pre-activation)
   bool use_rfwd01() const {
     return g_options.rfwd01 != 0 && rf_img && f16 && split_on() && use_tail() && planes_l0() &&
-           rfwd01_eligible(L, w.data(), wp.data()) && (int64_t)x_mpad <= ((int64_t)1 << 23);
+           rfwd01_eligible(L, w.data(), wp.data()) && rfwd01_rows_ok(x_mpad);
   }
   // the forward's layers 0 and 1 in one launch (rfwd.hip fwd01_kernel): tanh layers of 256, X on its planes
   bool use_fwd01() const {
     return g_options.fwd01 != 0 && fw_img && f16 && split_on() && planes_l0() && fwd01_eligible(L, w.data(), wp.data()) &&
-           (int64_t)x_mpad <= ((int64_t)1 << 23);
+           rfwd01_rows_ok(x_mpad);
   }
   bool use_rbwd0() const {
     return g_options.rbwd0 != 0 && f16 && x_planes && rbwd0_geom() && g_options.planes != 0 && split_on() &&
@@ -244,12 +280,7 @@ struct trpo_engine {
     a.x_mpad = x_mpad;
     a.x_ldp = x_ldp;
     a.eX = pl_e;
-    a.splits = active_splits;
-    a.rows_per_split = rows_per_split;
-    a.slab = slab;
-    a.slab_stride = slab_stride;
-    a.off_w = offW[0];
-    a.off_b = offb[0];
+    a.dst = slab_dst(0);
     a.skip = skip;
     return a;
   }
@@ -752,20 +783,13 @@ struct trpo_engine {
     active_splits = (int)std::max<int64_t>(1, (n + rps - 1) / rps);
   }
   int active_splits = 1;
+  // where the launches that follow write layer l's weight-gradient block, under the geometry above
+  SlabDst slab_dst(int l) const { return SlabDst{active_splits, rows_per_split, slab, slab_stride, offW[l], offb[l]}; }
 
-  void copy_in(void* dst, const void* src, size_t bytes, int mem) {
-    if (bytes == 0) return;
-    HIPCHECK(hipMemcpyAsync(dst, src, bytes, mem == TRPO_MEM_DEVICE ? hipMemcpyDeviceToDevice
-                                                                     : hipMemcpyHostToDevice,
-                            stream));
-    if (mem != TRPO_MEM_DEVICE) HIPCHECK(hipStreamSynchronize(stream));
-  }
+  void copy_in(void* dst, const void* src, size_t bytes, int mem) { trpo_abi::copy_in(dst, src, bytes, mem, stream); }
   void copy_out(void* dst, const void* src, size_t bytes, int mem) {
     if (bytes == 0) return;
-    HIPCHECK(hipMemcpyAsync(dst, src, bytes, mem == TRPO_MEM_DEVICE ? hipMemcpyDeviceToDevice
-                                                                     : hipMemcpyDeviceToHost,
-                            stream));
-    HIPCHECK(hipStreamSynchronize(stream));
+    trpo_abi::copy_out(dst, src, bytes, mem, stream);
     har_pending = false;
     check_har();
   }
@@ -911,9 +935,9 @@ struct trpo_engine {
     check_launch();
   }
   void ensure_w3() {
-    if (split_on() && !w3_valid) {
+    if (split_on() && !cache.w3_valid) {
       split_parts(true, false, true, false, WF, WF3, nullptr, "split_w");
-      w3_valid = true;
+      cache.w3_valid = true;
     }
   }
 
@@ -1060,44 +1084,37 @@ struct trpo_engine {
   // policy forward + KL_ff plain backward at theta (cached over CG)
   void prepare() {
     require_batch();
-    if (prepared) return;
+    if (cache.prepared) return;
     PackArgs pa = pack_args(WF, &WB, 0);
     launch_pack(pa, theta, 0, nullptr, stream);
-    w3_valid = false;
-    chain_w_valid = false;
-    f16_w_valid = false;
+    // Only what the FVP path will read is written below (prep_e_top records it; fvp() re-prepares if the
+    // path changes)
+    cache.prepare_begins(e_top_needed(), use_fused16());
     ensure_w3();
     am_reset(am_d(0), L);
     am_reset(am_ds(L - 1), 1);
     if (use_fused16() && g_options.ls_fused == 1) fused16_forward(theta, true);   // fwd_loss16's prepare form
     else forward(WF, WF3, theta, H, RowEpi::kPrepHead, "fwd");
     // KL_ff plain backward: DH_l = D_l W_l^T ; D_{l-1} = DH (1-H^2) ; E_{l-1} = -2 DH H.
-    // Only what the FVP path will read is written (prep_e_top records it; fvp() re-prepares if the
-    // path changes): D_0 never (the R-backward stops at RD_0), E_{L-2} not under the fused tail, which
+    // D_0 is never written (the R-backward stops at RD_0), E_{L-2} not under the fused tail, which
     // recomputes it from H and D_{L-1}.
-    prep_e_top = e_top_needed();
-    prep_fused16 = use_fused16();
-    ds_ready = false;
-    pg_ready = false;
-    d1_plane = false;
-    d1_tiled = false;
-    const bool hb2 = use_hbwd2();
+    const bool prep_e_top = cache.prep_e_top, hb2 = use_hbwd2();
     if (use_fused16()) {
       // D_1, E_1, E_0 and the policy gradient's slabs in one launch on the f16 weight images (fused16.hip)
       fused16_w_images();
-      Fused16Args fa = fused16_args(nullptr, nullptr, pg_grid);
+      Fused16Args fa = fused16_args(nullptr, nullptr, cache.pg_grid);
       fa.D1out = L == 3 ? D[1] : nullptr;   // one hidden layer: E_0 only (D_1 is the head's delta)
       fa.E1out = L == 3 ? E[1] : nullptr;
       fa.E0out = E[0];
       fa.am_d1_out = L == 3 ? am_d(1) : nullptr;
       {
         Scope sp(this, "bwd_pg");
-        launch_prep_pg_fused16(fa, pg_grid, stream);
+        launch_prep_pg_fused16(fa, cache.pg_grid, stream);
         check_launch();
       }
-      pg_ready = true;
+      cache.pg_ready = true;
       reduce_losses(0, nullptr);
-      prepared = true;
+      cache.prepared = true;
       return;
     }
     for (int l = L - 1; l >= 1; --l) {
@@ -1123,26 +1140,18 @@ struct trpo_engine {
         hb.am_d1 = am_d(L - 2);
         hb.am_ds1 = am_ds(L - 2);
         PgSplits pgs(this);   // the slab block it writes is reduced with the policy gradient's
-        hb.splits = active_splits;
-        hb.rows_per_split = rows_per_split;
-        hb.slab = slab;   // the policy gradient's W_{L-1} / b_{L-1} block, reduced by policy_grad()
-        hb.slab_stride = slab_stride;
-        hb.off_w = offW[L - 1];
-        hb.off_b = offb[L - 1];
+        hb.dst = slab_dst(L - 1);   // the policy gradient's W_{L-1} / b_{L-1} block, reduced by policy_grad()
         if (L == 3 && D1h && eD1t && use_rbwd0() && wp[2] % 32 == 0 && n > 0) {
-          d1_mpad = (int)((n + 255) / 256 * 256);
+          cache.d1_mpad = (int)((n + 255) / 256 * 256);
           hb.D1h = D1h;
-          hb.d1_mpad = d1_mpad;
+          hb.d1_mpad = cache.d1_mpad;
           hb.eD1t = eD1t;
         }
         Scope sp(this, "bwd2_l2");
         launch_head_bwd2(hb, num_cus, stream);
         check_launch();
-        ds_ready = true;
-        if (hb.D1h) {
-          d1_plane = true;
-          d1_tiled = true;
-        }
+        cache.ds_ready = true;
+        cache.d1_plane = cache.d1_tiled = hb.D1h != nullptr;
         continue;
       }
       RowGemmArgs a = row_args(w[l], wp[l]);
@@ -1165,15 +1174,15 @@ struct trpo_engine {
       check_launch();
     }
     // D_1's hi plane for the fused R-backward (per update; the FVPs' D_1 V_1^T segment reads half the bytes)
-    if (!d1_plane && D1h && use_rbwd0() && n > 0) {
-      d1_mpad = (int)((n + 255) / 256 * 256);
+    if (!cache.d1_plane && D1h && use_rbwd0() && n > 0) {
+      cache.d1_mpad = (int)((n + 255) / 256 * 256);
       Scope sp(this, "split_d1");
-      launch_split_planes(D[1], (int)n, d1_mpad, wp[2], wp[2], D1h, nullptr, d1_ldp, am_d(1), pl_e + 1, stream);
+      launch_split_planes(D[1], (int)n, cache.d1_mpad, wp[2], wp[2], D1h, nullptr, d1_ldp, am_d(1), pl_e + 1, stream);
       check_launch();
-      d1_plane = true;
+      cache.d1_plane = true;
     }
     reduce_losses(0, nullptr);
-    prepared = true;
+    cache.prepared = true;
   }
 
   // sum over splits -> out (local partial) ; all-reduce
@@ -1186,12 +1195,7 @@ struct trpo_engine {
     allreduce_f32(out, (size_t)P);
   }
 
-  // every slab writer other than the policy gradient's own layers clears ds_ready: the head-layer block and
-  // DS_{L-2} that prepare() leaves for policy_grad() (hbwd.hip) are then recomputed instead of trusted
-  void wgrad_layer(int l, int nseg, WSeg s0, WSeg s1, int colsum_seg, const int* skip, const char* tag,
-                   bool keeps_pg_head = false) {
-    if (!keeps_pg_head) ds_ready = false;
-    pg_ready = false;
+  void wgrad_layer(int l, int nseg, WSeg s0, WSeg s1, int colsum_seg, const int* skip, const char* tag) {
     WGradArgs a{};
     a.rows = (int)n;
     a.Ma = w[l];
@@ -1202,12 +1206,7 @@ struct trpo_engine {
     a.seg[0] = s0;
     a.seg[1] = s1;
     a.colsum_seg = colsum_seg;
-    a.splits = active_splits;
-    a.rows_per_split = rows_per_split;
-    a.slab = slab;
-    a.slab_stride = slab_stride;
-    a.off_w = offW[l];
-    a.off_b = offb[l];
+    a.dst = slab_dst(l);
     a.skip = skip;
     a.f16 = f16;
     Scope sp(this, tag);
@@ -1220,18 +1219,18 @@ struct trpo_engine {
     reprepare_if_path_changed();
     prepare();
     if (use_fused16()) {
-      if (!pg_ready) pg_fused16();
-      ds_ready = false;
-      reduce_grad(g, nullptr, pg_grid);
+      if (!cache.pg_ready) pg_fused16();
+      reduce_grad(g, nullptr, cache.pg_grid);
       return;
     }
     ensure_w3();
     PgSplits pgs(this);
+    cache.slabs_written(/*keeps_pg_head=*/true);   // the layers below the head's write their blocks
     // surr backward: DS_{l-1} = (DS_l W_l^T)(1-H_l^2) ; DS of hidden layers lives in RD scratch
     std::vector<float*> DS(L);
     DS[L - 1] = DSL;
     for (int l = 0; l < L - 1; ++l) DS[l] = RD[l];
-    const bool have_ds = ds_ready;   // DS_{L-2} (and its running max) from the prepare pass (hbwd.hip)
+    const bool have_ds = cache.ds_ready;   // DS_{L-2} (and its running max) from the prepare pass (hbwd.hip)
     am_reset(am_ds(0), have_ds ? L - 2 : L - 1);
     const bool r0f = use_rbwd0();
     for (int l = have_ds ? L - 2 : L - 1; l >= 1; --l) {
@@ -1268,7 +1267,7 @@ struct trpo_engine {
       char t[32];
       std::snprintf(t, sizeof t, "pg_wgrad_l%d", l);
       wgrad_layer(l, 1, WSeg{act_in(l), DS[l], wp[l], wp[l + 1], l == 0 ? am_x() : nullptr, am_ds(l)}, WSeg{}, 0,
-                  nullptr, t, /*keeps_pg_head=*/true);
+                  nullptr, t);
     }
     reduce_grad(g, nullptr);
   }
@@ -1281,8 +1280,8 @@ struct trpo_engine {
     // the path changed since prepare(): E_{L-2} needed but not written, or the other side of the fused16 switch
     reprepare_if_path_changed();
     prepare();
-    ds_ready = false;   // the FVP's R-backward writes RD (DS_{L-2}'s scratch)
-    pg_ready = false;   // ... and every FVP path the slabs
+    cache.rd_written();      // the FVP's R-backward writes RD (DS_{L-2}'s scratch)
+    cache.slabs_written();   // ... and every FVP path the slabs
     if (use_fused16()) {
       fvp_fused16(v, out, skip, defer && !multi_rank() && cg_fused_reduce_ok(P) ? defer : nullptr);
       return;
@@ -1418,17 +1417,11 @@ struct trpo_engine {
       ta.am_out = am_rd(l - 1);
       ta.RDout = RD[l - 1];
       ta.invN = 1.0 / (double)n_global;
-      ta.splits = active_splits;
-      ta.rows_per_split = rows_per_split;
-      ta.slab = slab;
-      ta.slab_stride = slab_stride;
-      ta.off_w = offW[l];
-      ta.off_b = offb[l];
+      ta.dst = slab_dst(l);
       ta.skip = skip;
       char tag[32];
       std::snprintf(tag, sizeof tag, "fvp_tail_l%d", l);
       Scope sp(this, tag);
-      ds_ready = false;   // slab and RD writer
       launch_tail_pack(tp, stream);
       launch_fvp_tail(ta, stream);
       check_launch();
@@ -1444,17 +1437,16 @@ struct trpo_engine {
           a.nseg = 2;
           a.A0 = RD[1];
           a.A1 = D[1];
-          if (d1_plane) {
+          if (cache.d1_plane) {
             a.A1h = D1h;
-            a.a1_mpad = d1_mpad;
+            a.a1_mpad = cache.d1_mpad;
             a.eA1p = pl_e + 1;
-            if (d1_tiled) a.eA1t = eD1t;
+            if (cache.d1_tiled) a.eA1t = eD1t;
           }
           a.am_a0 = am_rd(1);
           a.am_a1 = am_d(1);
           a.E = E[0];
           a.RH = RH[1];
-          ds_ready = false;   // slab writer
           Scope sp(this, "fvp_rbwdwg_l1");
           launch_rbwd0(a, stream);
           check_launch();
@@ -1531,11 +1523,11 @@ struct trpo_engine {
 
   // the whole Hv in one launch (fused.hip) + the slab reduction
   void fvp_fused(const float* v, float* out, const int* skip) {
-    if (!chain_w_valid) {
+    if (!cache.chain_w_valid) {
       Scope sp(this, "fvp_img_w");
       launch_chain_img(chain_jobs, theta, v, 0, nullptr, stream);
       check_launch();
-      chain_w_valid = true;
+      cache.chain_w_valid = true;
     }
     {
       Scope sp(this, "fvp_img_v");
@@ -1593,11 +1585,11 @@ struct trpo_engine {
     return fa;
   }
   void fused16_w_images() {
-    if (f16_w_valid) return;
+    if (cache.f16_w_valid) return;
     Scope sp(this, "fvp_img_w");
     launch_fused16_img(f16_jobs, theta, nullptr, 0, nullptr, f16_e, stream);
     check_launch();
-    f16_w_valid = true;
+    cache.f16_w_valid = true;
   }
 
   // the whole Hv in one launch on the f16 split (fused16.hip) + the slab reduction
@@ -1632,22 +1624,23 @@ struct trpo_engine {
   // block of g (when the prepare launch's are gone)
   void pg_fused16() {
     fused16_w_images();
-    const Fused16Args fa = fused16_args(nullptr, nullptr, pg_grid);
+    cache.slabs_written();
+    const Fused16Args fa = fused16_args(nullptr, nullptr, cache.pg_grid);
     {
       Scope sp(this, "pg_fused");
-      launch_pg_fused16(fa, pg_grid, stream);
+      launch_pg_fused16(fa, cache.pg_grid, stream);
       check_launch();
     }
-    pg_ready = true;
+    cache.pg_ready = true;
   }
 
   // the same Hv with the row-local part (R-forward, R-head, R-backward) in one fused launch
   void fvp_chain(const float* v, float* out, const int* skip) {
-    if (!chain_w_valid) {
+    if (!cache.chain_w_valid) {
       Scope sp(this, "fvp_img_w");
       launch_chain_img(chain_jobs, theta, v, 0, nullptr, stream);
       check_launch();
-      chain_w_valid = true;
+      cache.chain_w_valid = true;
     }
     {
       Scope sp(this, "fvp_img_v");
@@ -1813,8 +1806,7 @@ struct trpo_engine {
     allreduce_f64(dscal + 1, 1);
     launch_adv_normalize(adv64, adv32, n, dscal, dscal + 1, inv_n, stream);
     check_launch();
-    prepared = false;
-    have_returns = true;
+    cache.advantages_computed();
   }
 
   // adv = (adv - mean)/(std + 1e-8) over all ranks (trpo_inksci.py:115-117), device arrays on this
@@ -1833,7 +1825,7 @@ struct trpo_engine {
 
   // 1 - var(y - ypred)/var(y) with y = returns, ypred = baseline (utils.py:208-211), f64 over all ranks
   double explained_variance() {
-    REQUIRE(have_returns, "no returns: compute the advantages first");
+    REQUIRE(cache.have_returns, "no returns: compute the advantages first");
     if (!ev_tmp) ev_tmp = dalloc<double>(cap);
     const double inv_n = 1.0 / (double)n_global;
     auto var = [&](const double* ypred, int slot) {
@@ -1888,7 +1880,7 @@ struct trpo_engine {
   // hipGraph of update_prefix: keyed on everything that shapes its launches (rows, the update
   // parameters that become kernel arguments, the baseline switch, the kernel-variant options).
   // The first update with a key runs eagerly (lazy allocations happen there), the second captures
-  // and replays, later ones replay.  Host flags the prefix leaves behind are restored after a replay.
+  // and replays, later ones replay.  The cache state the prefix leaves behind is restored after a replay.
   struct GraphKey {
     int64_t n, n_global;
     const void* comm;   // the communicator / host transport the all-reduces were captured with
@@ -1931,11 +1923,7 @@ struct trpo_engine {
   hipGraphExec_t upd_exec = nullptr;
   GraphKey upd_key{};
   bool upd_key_seen = false, graphs_broken = false;
-  struct PrefixFlags {
-    bool prepared, w3_valid, chain_w_valid, f16_w_valid, have_returns, prep_e_top, prep_fused16, ds_ready, pg_ready,
-        d1_plane, d1_tiled;
-    int pg_grid;
-  } upd_flags{};
+  CacheState upd_state{};   // `cache` as the captured prefix left it
   void drop_graph() {
     if (upd_exec) {
       if (har_graph_end) (void)hipStreamSynchronize(stream);   // its host nodes may still be pending
@@ -1957,18 +1945,7 @@ struct trpo_engine {
     if (same && upd_exec) {
       HIPCHECK(hipGraphLaunch(upd_exec, stream));
       if (har_graph_end) har_pending = true;
-      prepared = upd_flags.prepared;
-      w3_valid = upd_flags.w3_valid;
-      chain_w_valid = upd_flags.chain_w_valid;
-      f16_w_valid = upd_flags.f16_w_valid;
-      have_returns = upd_flags.have_returns;
-      prep_e_top = upd_flags.prep_e_top;
-      prep_fused16 = upd_flags.prep_fused16;
-      ds_ready = upd_flags.ds_ready;
-      pg_ready = upd_flags.pg_ready;
-      pg_grid = upd_flags.pg_grid;
-      d1_plane = upd_flags.d1_plane;
-      d1_tiled = upd_flags.d1_tiled;
+      cache = upd_state;
       return;
     }
     if (!same) {
@@ -1980,7 +1957,7 @@ struct trpo_engine {
       return;
     }
     // capture (the cache is rebuilt inside the graph, so the prefix must not skip prepare())
-    prepared = false;
+    cache.prepared = false;
     hipGraph_t graph = nullptr;
     har_next = 0;
     HIPCHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
@@ -1999,12 +1976,11 @@ struct trpo_engine {
       upd_exec = nullptr;
       graphs_broken = true;
       (void)hipGetLastError();
-      prepared = false;
+      cache.prepared = false;
       update_prefix(prm);
       return;
     }
-    upd_flags = PrefixFlags{prepared,   w3_valid, chain_w_valid, f16_w_valid, have_returns, prep_e_top,
-                            prep_fused16, ds_ready, pg_ready,    d1_plane,    d1_tiled,     pg_grid};
+    upd_state = cache;
     har_graph_end = har_next;   // the graph's host nodes own these slots from now on
     HIPCHECK(hipGraphLaunch(upd_exec, stream));
     if (har_graph_end) har_pending = true;
@@ -2029,7 +2005,7 @@ struct trpo_engine {
     // sff(theta) ; losses ; revert if kl > 2 max_kl  (:154-158)
     launch_ls_finalize(theta_prev, fullstep, theta, theta_ls, P, sc, stream);
     check_launch();
-    prepared = false;
+    cache.theta_changed();
     fetch_scalars();
     if (st) {
       st->cg_iters = hsc->iters;
@@ -2166,7 +2142,7 @@ int trpo_set_flat(trpo_engine* e, const float* theta, int mem) {
     REQUIRE(e && theta, "NULL argument");
     e->use();
     e->copy_in(e->theta, theta, e->P * sizeof(float), mem);
-    e->prepared = false;
+    e->cache.theta_changed();
   });
 }
 
@@ -2239,9 +2215,8 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
     REQUIRE(!bad, "action index out of range [0, n_actions)");
     if (advant) e->copy_in(e->adv32, advant, (size_t)n * sizeof(float), mem);
     e->set_splits();
-    e->prepared = false;
+    e->cache.batch_changed();
     e->have_rewards = false;
-    e->have_returns = false;
     e->have_tail = false;
   });
 }
@@ -2257,7 +2232,7 @@ int trpo_set_rewards(trpo_engine* e, const double* rewards, const uint8_t* start
     e->have_baseline = baseline != nullptr;
     if (baseline) e->copy_in(e->baseline, baseline, (size_t)e->n * sizeof(double), mem);
     e->have_rewards = true;
-    e->have_returns = false;
+    e->cache.rewards_changed();
     e->have_tail = false;
   });
 }
@@ -2314,52 +2289,30 @@ int trpo_standardize(trpo_engine* e, double* adv, int64_t n, int64_t n_global, f
     if (e) e->use();
     if (n_global == 0) return;
     hipStream_t s = e ? e->stream : nullptr;
-    std::vector<void*> tmps;
-    auto dev = [&](size_t bytes) {
-      void* ptr = nullptr;
-      HIPCHECK(hipMalloc(&ptr, std::max<size_t>(bytes, 16)));
-      tmps.push_back(ptr);
-      return ptr;
-    };
-    try {
-      const bool host = mem != TRPO_MEM_DEVICE;
-      double* da = adv;
-      float* d32 = adv32_out;
-      if (host) {
-        da = static_cast<double*>(dev((size_t)n * sizeof(double)));
-        copy_in(da, adv, (size_t)n * sizeof(double), TRPO_MEM_HOST, s);
-        d32 = adv32_out ? static_cast<float*>(dev((size_t)n * sizeof(float))) : nullptr;
-      }
-      if (e) {
-        e->standardize(da, d32, n, n_global);
-      } else {
-        double* part = static_cast<double*>(dev(kRedBlocks * sizeof(double)));
-        double* sums = static_cast<double*>(dev(2 * sizeof(double)));
-        const double inv_n = 1.0 / (double)n;
-        launch_adv_center_partials(da, nullptr, da, n, part, s);
-        launch_sum_finish(part, sums, s);
-        launch_adv_sq_partials(da, n, sums, inv_n, part, s);
-        launch_sum_finish(part, sums + 1, s);
-        launch_adv_normalize(da, d32, n, sums, sums + 1, inv_n, s);
-        check_launch();
-      }
-      if (host) {
-        copy_out(adv, da, (size_t)n * sizeof(double), TRPO_MEM_HOST, s);
-        if (adv32_out) copy_out(adv32_out, d32, (size_t)n * sizeof(float), TRPO_MEM_HOST, s);
-      }
-      HIPCHECK(hipStreamSynchronize(s));
-      if (e) {
-        // the host all-reduce callbacks of the two sums ran during the sync: a failure there means the
-        // mean / std were rank-local, so it is this call's error (as fetch_scalars / copy_out report it)
-        e->har_pending = false;
-        e->check_har();
-      }
-    } catch (...) {
-      (void)hipStreamSynchronize(s);
-      for (void* t : tmps) (void)hipFree(t);
-      throw;
+    Staging st(mem, s);
+    double* da = st.inout(adv, (size_t)n);
+    float* d32 = st.out(adv32_out, (size_t)n);
+    if (e) {
+      e->standardize(da, d32, n, n_global);
+    } else {
+      double* part = st.tmp<double>(kRedBlocks);
+      double* sums = st.tmp<double>(2);
+      const double inv_n = 1.0 / (double)n;
+      launch_adv_center_partials(da, nullptr, da, n, part, s);
+      launch_sum_finish(part, sums, s);
+      launch_adv_sq_partials(da, n, sums, inv_n, part, s);
+      launch_sum_finish(part, sums + 1, s);
+      launch_adv_normalize(da, d32, n, sums, sums + 1, inv_n, s);
+      check_launch();
     }
-    for (void* t : tmps) HIPCHECK(hipFree(t));
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(s));
+    if (e) {
+      // the host all-reduce callbacks of the two sums ran during the sync: a failure there means the
+      // mean / std were rank-local, so it is this call's error (as fetch_scalars / copy_out report it)
+      e->har_pending = false;
+      e->check_har();
+    }
   });
 }
 
@@ -2378,7 +2331,7 @@ int trpo_eval_losses(trpo_engine* e, const float* theta, float out3[3], int mem)
     REQUIRE(e && theta && out3, "NULL argument");
     e->use();
     e->copy_in(e->theta, theta, e->P * sizeof(float), mem);   // sff(th), trpo_inksci.py:128
-    e->prepared = false;
+    e->cache.theta_changed();
     e->eval_losses_dev(e->theta);
     e->fetch_scalars();
     std::memcpy(out3, e->hsc->loss_trial, 3 * sizeof(float));
@@ -2540,20 +2493,10 @@ int trpo_linesearch(trpo_engine* e, const float* x, const float* fullstep, doubl
         break;
       }
     }
-    e->prepared = false;
+    e->cache.theta_changed();
     e->copy_out(theta_out, k_acc >= 0 ? e->theta_trial : e->theta_prev, P * sizeof(float), mem);
     if (k_out) *k_out = k_acc;
   });
-}
-
-void trpo_default_params(trpo_update_params* p) {
-  if (!p) return;
-  p->cg_iters = 10;
-  p->residual_tol = 1e-10f;
-  p->cg_damping = 0.1f;
-  p->max_kl = 0.01;
-  p->compute_advantages = 0;
-  p->gamma = 0.95;
 }
 
 int trpo_update(trpo_engine* e, const trpo_update_params* p, trpo_update_stats* stats) {
@@ -2565,28 +2508,6 @@ int trpo_update(trpo_engine* e, const trpo_update_params* p, trpo_update_stats* 
     if (p) prm = *p;
     e->update(prm, stats);
   });
-}
-
-int trpo_device_count(int* out) {
-  return guarded([&] {
-    REQUIRE(out, "NULL argument");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) n = 0;
-    (void)hipGetLastError();
-    *out = n;
-  });
-}
-
-void trpo_default_rollout_params(trpo_rollout_params* p) {
-  if (!p) return;
-  std::memset(p, 0, sizeof *p);
-  p->n_envs = 1;
-  p->max_pathlength = 1000;    // config["max_steps"] (trpo_inksci.py:17)
-  p->n_timesteps = 1000;       // config["episodes_per_roll"] (trpo_inksci.py:17, used as a step budget)
-  p->train = 1;
-  p->time_limit = 200;         // CartPole-v0 TimeLimit
-  p->seed = 1;
-  p->mem = TRPO_MEM_HOST;
 }
 
 int trpo_rollout_cartpole(trpo_engine* e, const trpo_rollout_params* p, int64_t* n_steps_out, int64_t* n_paths_out) {
@@ -2608,40 +2529,18 @@ int trpo_rollout_fetch(trpo_engine* e, double* obs, float* obs32, int64_t* actio
     const int64_t N = e->roll_n;
     const int obs_dim = e->w[0], A = e->w[e->L];
     RolloutOut o{};
-    std::vector<void*> tmps;
-    auto dst = [&](auto* user, size_t elems) {
-      using T = std::remove_pointer_t<decltype(user)>;
-      if (!user || mem == TRPO_MEM_DEVICE) return user;
-      void* ptr = nullptr;
-      HIPCHECK(hipMalloc(&ptr, std::max<size_t>(elems * sizeof(T), 16)));
-      tmps.push_back(ptr);
-      return static_cast<T*>(ptr);
-    };
-    o.obs64 = dst(obs, (size_t)N * obs_dim);
-    o.X = dst(obs32, (size_t)N * obs_dim);
+    Staging st(mem, e->stream);
+    o.obs64 = st.out(obs, (size_t)N * obs_dim);
+    o.X = st.out(obs32, (size_t)N * obs_dim);
     o.ldx = obs_dim;
-    o.actions64 = dst(actions, (size_t)N);
-    o.dist = dst(action_dists, (size_t)N * A);
-    o.rewards = dst(rewards, (size_t)N);
-    o.starts = dst(episode_starts, (size_t)N);
-    o.uniforms = dst(uniforms, (size_t)N);
-    try {
-      e->rollout_compact(o);
-      if (mem != TRPO_MEM_DEVICE) {
-        if (obs) e->copy_out(obs, o.obs64, (size_t)N * obs_dim * sizeof(double), mem);
-        if (obs32) e->copy_out(obs32, o.X, (size_t)N * obs_dim * sizeof(float), mem);
-        if (actions) e->copy_out(actions, o.actions64, (size_t)N * sizeof(int64_t), mem);
-        if (action_dists) e->copy_out(action_dists, o.dist, (size_t)N * A * sizeof(float), mem);
-        if (rewards) e->copy_out(rewards, o.rewards, (size_t)N * sizeof(double), mem);
-        if (episode_starts) e->copy_out(episode_starts, o.starts, (size_t)N, mem);
-        if (uniforms) e->copy_out(uniforms, o.uniforms, (size_t)N * sizeof(double), mem);
-      }
-      HIPCHECK(hipStreamSynchronize(e->stream));
-    } catch (...) {
-      for (void* t : tmps) (void)hipFree(t);
-      throw;
-    }
-    for (void* t : tmps) HIPCHECK(hipFree(t));
+    o.actions64 = st.out(actions, (size_t)N);
+    o.dist = st.out(action_dists, (size_t)N * A);
+    o.rewards = st.out(rewards, (size_t)N);
+    o.starts = st.out(episode_starts, (size_t)N);
+    o.uniforms = st.out(uniforms, (size_t)N);
+    e->rollout_compact(o);
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
   });
 }
 
@@ -2666,9 +2565,8 @@ int trpo_rollout_to_batch(trpo_engine* e, int64_t n_global) {
     e->n_global = n_global;
     e->update_x_amax();
     e->set_splits();
-    e->prepared = false;
+    e->cache.batch_changed();
     e->have_rewards = true;
-    e->have_returns = false;
     e->have_baseline = false;
     e->have_tail = false;
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -2690,7 +2588,7 @@ int trpo_get_feed_view(trpo_engine* e, trpo_feed_view* v) {
     v->old_dist = e->old;
     v->ld_old = e->wp[e->L];
     v->episode_starts = e->have_rewards ? e->starts : nullptr;
-    v->returns = e->have_returns ? e->returns : nullptr;   // stale until the advantages are computed
+    v->returns = e->cache.have_returns ? e->returns : nullptr;   // stale until the advantages are computed
     v->baseline = e->baseline;
   });
 }
@@ -2722,231 +2620,15 @@ int trpo_act(trpo_engine* e, const float* states, int64_t n, const double* unifo
     e->use();
     if (n == 0) return;
     const int obs = e->w[0], A = e->w[e->L];
-    const float* s = states;
-    const double* r = uniforms;
-    int64_t* ao = actions_out;
-    float* dout = dists_out;
-    std::vector<void*> tmps;
-    auto dev = [&](size_t bytes) {
-      void* ptr = nullptr;
-      HIPCHECK(hipMalloc(&ptr, std::max<size_t>(bytes, 16)));
-      tmps.push_back(ptr);
-      return ptr;
-    };
-    try {
-      if (mem != TRPO_MEM_DEVICE) {
-        float* ds = static_cast<float*>(dev((size_t)n * obs * sizeof(float)));
-        e->copy_in(ds, states, (size_t)n * obs * sizeof(float), mem);
-        s = ds;
-        if (uniforms) {
-          double* dr = static_cast<double*>(dev((size_t)n * sizeof(double)));
-          e->copy_in(dr, uniforms, (size_t)n * sizeof(double), mem);
-          r = dr;
-        }
-        if (actions_out) ao = static_cast<int64_t*>(dev((size_t)n * sizeof(int64_t)));
-        if (dists_out) dout = static_cast<float*>(dev((size_t)n * A * sizeof(float)));
-      }
-      launch_act(e->policy_shape(), e->theta, e->max_width(), s, n, r, train, ao, dout, e->stream);
-      check_launch();
-      if (mem != TRPO_MEM_DEVICE) {
-        if (actions_out) e->copy_out(actions_out, ao, (size_t)n * sizeof(int64_t), mem);
-        if (dists_out) e->copy_out(dists_out, dout, (size_t)n * A * sizeof(float), mem);
-      }
-      HIPCHECK(hipStreamSynchronize(e->stream));
-    } catch (...) {
-      for (void* t : tmps) (void)hipFree(t);
-      throw;
-    }
-    for (void* t : tmps) HIPCHECK(hipFree(t));
-  });
-}
-
-namespace {
-// engine-free kernels on the current device: stage host arrays in plain hipMalloc buffers
-struct Scratch {
-  std::vector<void*> p;
-  void* get(size_t bytes) {
-    void* ptr = nullptr;
-    HIPCHECK(hipMalloc(&ptr, std::max<size_t>(bytes, 16)));
-    p.push_back(ptr);
-    return ptr;
-  }
-  ~Scratch() {
-    for (void* x : p) (void)hipFree(x);
-  }
-};
-}  // namespace
-
-int trpo_cat_sample(const float* prob, int64_t n, int k, const double* r, int64_t* out, int mem) {
-  return guarded([&] {
-    REQUIRE(prob && r && out && n >= 0 && k >= 1, "bad argument");
-    if (n == 0) return;
-    Scratch sc;
-    const float* dp = prob;
-    const double* dr = r;
-    int64_t* dout = out;
-    if (mem != TRPO_MEM_DEVICE) {
-      float* a = static_cast<float*>(sc.get((size_t)n * k * sizeof(float)));
-      double* b = static_cast<double*>(sc.get((size_t)n * sizeof(double)));
-      HIPCHECK(hipMemcpy(a, prob, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice));
-      HIPCHECK(hipMemcpy(b, r, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-      dp = a;
-      dr = b;
-      dout = static_cast<int64_t*>(sc.get((size_t)n * sizeof(int64_t)));
-    }
-    launch_cat_sample(dp, n, k, dr, dout, nullptr);
+    Staging st(mem, e->stream);
+    const float* s = st.in(states, (size_t)n * obs);
+    const double* r = st.in(uniforms, (size_t)n);
+    int64_t* ao = st.out(actions_out, (size_t)n);
+    float* dout = st.out(dists_out, (size_t)n * A);
+    launch_act(e->policy_shape(), e->theta, e->max_width(), s, n, r, train, ao, dout, e->stream);
     check_launch();
-    if (mem != TRPO_MEM_DEVICE) HIPCHECK(hipMemcpy(out, dout, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    HIPCHECK(hipDeviceSynchronize());
-  });
-}
-
-int trpo_cartpole_step(const double* state, const int64_t* action, int64_t n, double* state_out, double* reward,
-                       uint8_t* done, int mem) {
-  return guarded([&] {
-    REQUIRE(state && action && state_out && n >= 0, "bad argument");
-    if (n == 0) return;
-    Scratch sc;
-    const double* ds = state;
-    const int64_t* da = action;
-    double *dso = state_out, *dr = reward;
-    uint8_t* dd = done;
-    if (mem != TRPO_MEM_DEVICE) {
-      double* a = static_cast<double*>(sc.get((size_t)n * 4 * sizeof(double)));
-      int64_t* b = static_cast<int64_t*>(sc.get((size_t)n * sizeof(int64_t)));
-      HIPCHECK(hipMemcpy(a, state, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHECK(hipMemcpy(b, action, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-      ds = a;
-      da = b;
-      dso = static_cast<double*>(sc.get((size_t)n * 4 * sizeof(double)));
-      dr = reward ? static_cast<double*>(sc.get((size_t)n * sizeof(double))) : nullptr;
-      dd = done ? static_cast<uint8_t*>(sc.get((size_t)n)) : nullptr;
-    }
-    launch_cartpole_step(ds, da, n, dso, dr, dd, nullptr);
-    check_launch();
-    if (mem != TRPO_MEM_DEVICE) {
-      HIPCHECK(hipMemcpy(state_out, dso, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-      if (reward) HIPCHECK(hipMemcpy(reward, dr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-      if (done) HIPCHECK(hipMemcpy(done, dd, (size_t)n, hipMemcpyDeviceToHost));
-    }
-    HIPCHECK(hipDeviceSynchronize());
-  });
-}
-
-int trpo_discount(const double* x, const uint8_t* starts, int64_t n, double gamma, double* out, int mem) {
-  return guarded([&] {
-    REQUIRE(x && out, "NULL argument");
-    REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return;
-    hipStream_t s = nullptr;
-    double *dx = nullptr, *dy = nullptr;
-    uint8_t* ds = nullptr;
-    void* ws = nullptr;
-    const bool dev = mem == TRPO_MEM_DEVICE;
-    HIPCHECK(hipMalloc(&ws, discount_workspace_bytes(n)));
-    if (!dev) {
-      HIPCHECK(hipMalloc(&dx, n * sizeof(double)));
-      HIPCHECK(hipMalloc(&dy, n * sizeof(double)));
-      HIPCHECK(hipMemcpy(dx, x, n * sizeof(double), hipMemcpyHostToDevice));
-    }
-    HIPCHECK(hipMalloc(&ds, n));
-    if (starts)
-      HIPCHECK(hipMemcpy(ds, starts, n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    else
-      HIPCHECK(hipMemset(ds, 0, n));
-    launch_discount(dev ? x : dx, ds, n, gamma, dev ? out : dy, ws, s);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipDeviceSynchronize());
-    if (!dev) HIPCHECK(hipMemcpy(out, dy, n * sizeof(double), hipMemcpyDeviceToHost));
-    (void)hipFree(ws);
-    (void)hipFree(ds);
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-  });
-}
-
-int trpo_gae(const double* rewards, const double* values, const uint8_t* starts, const double* tail_values,
-             int64_t n, double gamma, double lambda, double* adv_out, double* returns_out, int mem) {
-  return guarded([&] {
-    REQUIRE(n >= 0, "n < 0");
-    REQUIRE(lambda >= 0.0 && lambda <= 1.0, "lambda must be in [0, 1]");
-    if (n == 0) return;
-    REQUIRE(rewards, "rewards is NULL");
-    const bool dev = mem == TRPO_MEM_DEVICE;
-    hipStream_t s = nullptr;
-    std::vector<void*> tmps;
-    auto alloc = [&](size_t bytes) {
-      void* ptr = nullptr;
-      HIPCHECK(hipMalloc(&ptr, std::max<size_t>(bytes, 16)));
-      tmps.push_back(ptr);
-      return ptr;
-    };
-    // a host input becomes a device copy; a device input is read in place
-    auto in = [&](const void* src, size_t bytes) -> const void* {
-      if (!src || dev) return src;
-      void* d = alloc(bytes);
-      HIPCHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-      return d;
-    };
-    try {
-      const size_t nd = (size_t)n * sizeof(double);
-      const double* dr = static_cast<const double*>(in(rewards, nd));
-      const double* dv = static_cast<const double*>(in(values, nd));
-      const uint8_t* ds = static_cast<const uint8_t*>(in(starts, (size_t)n));
-      const double* dt = static_cast<const double*>(in(tail_values, nd));
-      double* da = adv_out && !dev ? static_cast<double*>(alloc(nd)) : adv_out;
-      double* dret = returns_out && !dev ? static_cast<double*>(alloc(nd)) : returns_out;
-      void* ws = alloc(gae_workspace_bytes(n));
-      launch_gae(dr, dv, ds, dt, n, gamma, lambda, da, dret, ws, s);
-      check_launch();
-      HIPCHECK(hipDeviceSynchronize());
-      if (!dev) {
-        if (adv_out) HIPCHECK(hipMemcpy(adv_out, da, nd, hipMemcpyDeviceToHost));
-        if (returns_out) HIPCHECK(hipMemcpy(returns_out, dret, nd, hipMemcpyDeviceToHost));
-      }
-    } catch (...) {
-      for (void* ptr : tmps) (void)hipFree(ptr);
-      throw;
-    }
-    for (void* ptr : tmps) (void)hipFree(ptr);
-  });
-}
-
-static int* option_slot(const std::string& k) {
-  if (k == "split_mfma") return &g_options.split_mfma;
-  if (k == "split_wg") return &g_options.split_wg;
-  if (k == "chain") return &g_options.chain;
-  if (k == "split_f16") return &g_options.split_f16;
-  if (k == "split_min_k") return &g_options.split_min_k;
-  if (k == "graphs") return &g_options.graphs;
-  if (k == "tail") return &g_options.tail;
-  if (k == "fused") return &g_options.fused;
-  if (k == "low_seg") return &g_options.low_seg;
-  if (k == "planes") return &g_options.planes;
-  if (k == "rbwd0") return &g_options.rbwd0;
-  if (k == "hbwd2") return &g_options.hbwd2;
-  if (k == "head_fwd") return &g_options.head_fwd;
-  if (k == "splits") return &g_options.splits;
-  if (k == "pg_splits") return &g_options.pg_splits;
-  if (k == "ls_fused") return &g_options.ls_fused;
-  if (k == "cg_fuse_reduce") return &g_options.cg_fuse_reduce;
-  if (k == "rfwd01") return &g_options.rfwd01;
-  if (k == "fwd01") return &g_options.fwd01;
-  if (k == "cg_p_img") return &g_options.cg_p_img;
-  throw ArgError("unknown option " + k);
-}
-
-int trpo_set_option(const char* name, int value) {
-  return guarded([&] {
-    REQUIRE(name, "NULL argument");
-    *option_slot(name) = value;
-  });
-}
-
-int trpo_get_option(const char* name, int* value) {
-  return guarded([&] {
-    REQUIRE(name && value, "NULL argument");
-    *value = *option_slot(name);
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
   });
 }
 

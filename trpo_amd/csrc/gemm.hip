@@ -497,8 +497,8 @@ wgrad3_kernel(const WGradArgs args) {
   const int wm = wave % WM, wn = wave / WM;
   const int lr = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, split = blockIdx.z;
-  const int r0 = split * args.rows_per_split;
-  const int r1 = min(args.rows, r0 + args.rows_per_split);
+  const int r0 = split * args.dst.rows_per_split;
+  const int r1 = min(args.rows, r0 + args.dst.rows_per_split);
   const int nk = r1 > r0 ? (r1 - r0 + BK - 1) / BK : 0;
   const int ntiles = nk * args.nseg;
   const bool do_colsum = (blockIdx.x == 0);
@@ -745,7 +745,7 @@ wgrad3_kernel(const WGradArgs args) {
     scale_acc<TM, TN>(acc, -(eA[last] + eB[last]));
   }
 
-  float* out = args.slab + (size_t)split * args.slab_stride;
+  float* out = args.dst.slab + (size_t)split * args.dst.slab_stride;
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -755,7 +755,7 @@ wgrad3_kernel(const WGradArgs args) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int i = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (i < args.Ma) out[args.off_w + (int64_t)i * args.Nb + j] = acc[tm][tn][r];
+        if (i < args.Ma) out[args.dst.off_w + (int64_t)i * args.Nb + j] = acc[tm][tn][r];
       }
     }
   if (do_colsum) {
@@ -767,7 +767,7 @@ wgrad3_kernel(const WGradArgs args) {
     }
     __syncthreads();
     for (int c = tid; c < BN; c += NT)
-      if (n0 + c < args.Nb) out[args.off_b + n0 + c] = cs_sh[0][c] + cs_sh[1][c];
+      if (n0 + c < args.Nb) out[args.dst.off_b + n0 + c] = cs_sh[0][c] + cs_sh[1][c];
   }
 }
 
@@ -831,8 +831,8 @@ wgrad_kernel(const WGradArgs args) {
   const int wm = wave % WM, wn = wave / WM;
   const int lr = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, split = blockIdx.z;
-  const int r0 = split * args.rows_per_split;
-  const int r1 = min(args.rows, r0 + args.rows_per_split);
+  const int r0 = split * args.dst.rows_per_split;
+  const int r1 = min(args.rows, r0 + args.dst.rows_per_split);
   const int nk = r1 > r0 ? (r1 - r0 + BK - 1) / BK : 0;
   const int ntiles = nk * args.nseg;
   const bool do_colsum = (blockIdx.x == 0);
@@ -964,7 +964,7 @@ wgrad_kernel(const WGradArgs args) {
     }
   }
 
-  float* out = args.slab + (size_t)split * args.slab_stride;
+  float* out = args.dst.slab + (size_t)split * args.dst.slab_stride;
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -974,10 +974,10 @@ wgrad_kernel(const WGradArgs args) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int i = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (i < args.Ma) out[args.off_w + (int64_t)i * args.Nb + j] = acc[tm][tn][r];
+        if (i < args.Ma) out[args.dst.off_w + (int64_t)i * args.Nb + j] = acc[tm][tn][r];
       }
     }
-  if (do_colsum && tid < BN && n0 + tid < args.Nb) out[args.off_b + n0 + tid] = csum;
+  if (do_colsum && tid < BN && n0 + tid < args.Nb) out[args.dst.off_b + n0 + tid] = csum;
 }
 
 template <int WM, int WN, int TM, int TN, int BKT, int EPI, int PF = 1>
@@ -1053,19 +1053,19 @@ void launch_row_epi(const RowGemmArgs& a, hipStream_t s) {
 template <int WM, int WN, int TM, int TN, int BKT = 16, int PF = 1>
 void launch_wg_cfg(const WGradArgs& a, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  dim3 grid((a.Ma + BM - 1) / BM, (a.Nb + BN - 1) / BN, a.splits);
+  dim3 grid((a.Ma + BM - 1) / BM, (a.Nb + BN - 1) / BN, a.dst.splits);
   hipLaunchKernelGGL((wgrad_kernel<WM, WN, TM, TN, BKT, PF>), grid, dim3(WM * WN * 64), 0, s, a);
 }
 
 template <int WM, int WN, int TM, int TN, int OCC, int PF>
 void launch_wg3_cfg(const WGradArgs& a, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  if (a.rows_per_split % 16) throw std::runtime_error("split-bf16 wgrad: rows_per_split % 16");
+  if (a.dst.rows_per_split % 16) throw std::runtime_error("split-bf16 wgrad: rows_per_split % 16");
   if (a.nseg > 1 && (a.seg[1].lda != a.seg[0].lda || a.seg[1].ldb != a.seg[0].ldb))
     throw std::runtime_error("split-bf16 wgrad: segments with different leading dimensions");
-  if ((int64_t)a.rows_per_split * (a.seg[0].lda > a.seg[0].ldb ? a.seg[0].lda : a.seg[0].ldb) * 4 >= (int64_t(1) << 30))
+  if ((int64_t)a.dst.rows_per_split * (a.seg[0].lda > a.seg[0].ldb ? a.seg[0].lda : a.seg[0].ldb) * 4 >= (int64_t(1) << 30))
     throw std::runtime_error("split-bf16 wgrad: a split's rows exceed the 1 GiB buffer-descriptor range");
-  dim3 grid((a.Ma + BM - 1) / BM, (a.Nb + BN - 1) / BN, a.splits);
+  dim3 grid((a.Ma + BM - 1) / BM, (a.Nb + BN - 1) / BN, a.dst.splits);
   WGradArgs b = a;
   b.low_seg = g_options.low_seg;
   if (a.f16)
@@ -1117,7 +1117,7 @@ void launch_rowgemm(const RowGemmArgs& a, hipStream_t s) {
 }
 
 void launch_wgrad(const WGradArgs& a, hipStream_t s) {
-  if (a.splits <= 0) return;
+  if (a.dst.splits <= 0) return;
   const int Mp = a.Ma, Np = a.Nb;
   // output tile by (fan_in, fan_out); every B column set of one split lives in one block row
   if (Np <= 32) {

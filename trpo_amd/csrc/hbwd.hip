@@ -43,14 +43,14 @@ __global__ void __launch_bounds__(kHbThreads) head_bwd2_kernel(const HeadBwd2Arg
   float mx1 = 0.0f, mx2 = 0.0f;
   // the policy gradient's last-layer weight gradient over this split's rows (slab != NULL): gw[j] = sum_r H[r][c]
   // DS2[r][j], column c's row of the W block, and the bias column sum of DS2 (thread j < A)
-  const bool wg = a.slab != nullptr;
+  const bool wg = a.dst.slab != nullptr;
   float gw[AT];
 #pragma unroll
   for (int j = 0; j < AT; ++j) gw[j] = 0.0f;
   float gb = 0.0f;
   // workgroup s walks split s's rows (the weight-gradient slabs' partition, engine set_splits)
-  const int r0 = blockIdx.x * a.rows_per_split;
-  const int r1 = min(a.rows, r0 + a.rows_per_split);
+  const int r0 = blockIdx.x * a.dst.rows_per_split;
+  const int r1 = min(a.rows, r0 + a.dst.rows_per_split);
   // one tile ahead in registers: column c of the tile's 32 H rows, and this thread's share of the head deltas
   // (2 x 32 x AT floats over 256 threads); they move to LDS at the top of the tile, so the next tile's loads
   // are in flight during this tile's FMAs
@@ -142,13 +142,13 @@ __global__ void __launch_bounds__(kHbThreads) head_bwd2_kernel(const HeadBwd2Arg
     }
   }
   if (wg) {
-    float* out = a.slab + (size_t)blockIdx.x * a.slab_stride;
+    float* out = a.dst.slab + (size_t)blockIdx.x * a.dst.slab_stride;
     if (c < a.N) {
 #pragma unroll
       for (int j = 0; j < AT; ++j)
-        if (j < a.A) out[a.off_w + (int64_t)c * a.A + j] = gw[j];
+        if (j < a.A) out[a.dst.off_w + (int64_t)c * a.A + j] = gw[j];
     }
-    if (c < a.A) out[a.off_b + c] = gb;
+    if (c < a.A) out[a.dst.off_b + c] = gb;
   }
   // running maxima of both outputs (the f16 split scales of their consumers): one atomicMax per workgroup
 #pragma unroll
@@ -210,12 +210,12 @@ __global__ void __launch_bounds__(kHmW * 64, 2) head_bwd2m_kernel(const HeadBwd2
     const int j = 2 * s + lh;
     wf[s] = (cv && j < a.A) ? a.WB[(size_t)j * a.Npad + col] : 0.0f;
   }
-  const bool wg = a.slab != nullptr;
+  const bool wg = a.dst.slab != nullptr;
   f32x16 gw = f32x16{};   // H^T DS2 over the split: lane = action, registers = columns 32w + r(i) + 4h
   float gb = 0.0f;        // DS2 column sums (thread j < A)
   float mx1 = 0.0f, mx2 = 0.0f;
-  const int r0 = blockIdx.x * a.rows_per_split;
-  const int r1 = min(a.rows, r0 + a.rows_per_split);
+  const int r0 = blockIdx.x * a.dst.rows_per_split;
+  const int r1 = min(a.rows, r0 + a.dst.rows_per_split);
   auto desc = [&](const void* p, int t0, int ld, int esz) {
     const int nr = max(0, min(kHbRows, r1 - t0));
     return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p + (size_t)t0 * ld * esz), 0, nr * ld * esz,
@@ -316,15 +316,15 @@ __global__ void __launch_bounds__(kHmW * 64, 2) head_bwd2m_kernel(const HeadBwd2
     }
   }
   if (wg) {
-    float* out = a.slab + (size_t)blockIdx.x * a.slab_stride;
+    float* out = a.dst.slab + (size_t)blockIdx.x * a.dst.slab_stride;
     if (lr < a.A) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int c = 32 * w + roff(i) + 4 * lh;
-        if (c < a.N) out[a.off_w + (int64_t)c * a.A + lr] = gw[i];
+        if (c < a.N) out[a.dst.off_w + (int64_t)c * a.A + lr] = gw[i];
       }
     }
-    if (tid < a.A) out[a.off_b + tid] = gb;
+    if (tid < a.A) out[a.dst.off_b + tid] = gb;
   }
   // running maxima of both outputs (the f16 split scales of their consumers): one atomicMax per workgroup
 #pragma unroll
@@ -360,9 +360,9 @@ void launch_head_bwd2(const HeadBwd2Args& a, int num_cus, hipStream_t s) {
   if (a.D1h && (!a.eD1t || a.d1_mpad < a.rows || a.Npad % 32))
     throw std::runtime_error("head_bwd2: hi plane without its exponents or stride");
   (void)num_cus;
-  if (a.splits <= 0 || a.rows_per_split % kHbRows || (int64_t)a.splits * a.rows_per_split < a.rows)
+  if (a.dst.splits <= 0 || a.dst.rows_per_split % kHbRows || (int64_t)a.dst.splits * a.dst.rows_per_split < a.rows)
     throw std::runtime_error("head_bwd2: splits do not cover the rows in 32-row tiles");
-  const int grid = a.splits;
+  const int grid = a.dst.splits;
   if (g_options.hbwd2 == 2) {
     switch ((a.A + 1) / 2) {
 #define HBM_CASE(k) case k: hipLaunchKernelGGL(head_bwd2m_kernel<k>, dim3(grid), dim3(kHmW * 64), 0, s, a); break;

@@ -184,6 +184,15 @@ void launch_split_b(const SplitArgs& a, const int* skip, hipStream_t s);
 //   slab[split][off_w + i*Nb + j] = sum_seg sum_rows A_seg[r][i] B_seg[r][j]
 //   slab[split][off_b + j]        = sum_rows B_{colsum_seg}[r][j]
 // ---------------------------------------------------------------------------
+// Where a split-K launch puts one layer's block of a flat parameter-shaped gradient: split s covers rows
+// [s * rows_per_split, (s + 1) * rows_per_split) and writes slab[s * slab_stride + ...] (the header above)
+struct SlabDst {
+  int splits = 0, rows_per_split = 0;
+  float* slab = nullptr;
+  int64_t slab_stride = 0;   // floats between consecutive splits
+  int64_t off_w = 0, off_b = 0;
+};
+
 struct WSeg {
   const float* A;  // [rows][lda]
   const float* B;  // [rows][ldb]
@@ -199,10 +208,7 @@ struct WGradArgs {
   int nseg;
   WSeg seg[2];
   int colsum_seg;      // B of this segment is column-summed into the bias slot
-  int splits, rows_per_split;  // rows_per_split multiple of 16
-  float* slab;
-  int64_t slab_stride; // floats between consecutive splits
-  int64_t off_w, off_b;
+  SlabDst dst;         // rows_per_split multiple of 16
   const int* skip;
   int f16 = 0;         // split path: scaled f16 (3 products) instead of bf16 (6 products)
   int low_seg = 0;     // f16: as RowGemmArgs::low_seg (set at launch)
@@ -523,9 +529,7 @@ struct TailArgs {
   unsigned* am_out;           // running max |RD_out|
   float* RDout;               // [rows][apad]  R-delta into the last hidden layer (RD_{L-2})
   double invN;
-  int splits, rows_per_split; // rows_per_split % 32 == 0
-  float* slab;
-  int64_t slab_stride, off_w, off_b;
+  SlabDst dst;                // rows_per_split % 32 == 0
   const int* skip;
 };
 struct TailPackArgs {
@@ -571,9 +575,7 @@ struct RBwd0Args {
   const uint16_t* Xl;
   int x_mpad, x_ldp;
   const int* eX;
-  int splits, rows_per_split;
-  float* slab;
-  int64_t slab_stride, off_w, off_b;
+  SlabDst dst;
   const int* skip;
   int low_seg = 0;          // f16: segment 1 on one product when it sits >= low_seg binades under (set at launch)
 };
@@ -597,12 +599,10 @@ struct HeadBwd2Args {
   int d1_mpad = 0;
   int* eD1t = nullptr;
   float* E1 = nullptr;       // E_{L-2} = -2 (D_{L-1} W^T) H (the kPrepBwd epilogue's second output), when read
-  // workgroup s takes the rows of split s (the weight-gradient slab partition); slab != NULL: it also writes the
-  // policy gradient's last-layer weight gradient (H^T DS2, W block [N][A] at off_w, bias colsum DS2 at off_b) of
-  // its rows into slab s
-  int splits = 0, rows_per_split = 0;
-  float* slab = nullptr;
-  int64_t slab_stride = 0, off_w = 0, off_b = 0;
+  // workgroup s takes the rows of split s (the weight-gradient slab partition); dst.slab != NULL: it also writes
+  // the policy gradient's last-layer weight gradient (H^T DS2, W block [N][A] at off_w, bias colsum DS2 at off_b)
+  // of its rows into slab s
+  SlabDst dst;
 };
 bool head_bwd2_eligible(int A, int Npad);
 // The softmax head forward with one state per lane (hbwd.hip): z = H W + b (K = last hidden width, A <= 32 actions),
@@ -660,6 +660,10 @@ struct Fwd01Args {
   const uint16_t* img;               // fwd01_img_bytes()
   const unsigned *am_w0, *am_w1;     // the weights' running-max slots (the image's scales)
 };
+// both kernels address an X plane with signed 32-bit byte offsets: up to 4 k-blocks (obs <= 128) of x_mpad rows
+// of 64 bytes must stay under 2^31 (the engine takes the per-layer plane path beyond)
+constexpr bool rfwd01_rows_ok(int64_t x_mpad) { return 4 * x_mpad * 64 < (int64_t(1) << 31); }
+static_assert(rfwd01_rows_ok((1 << 23) - 256) && !rfwd01_rows_ok(1 << 23), "rfwd01 / fwd01 row limit");
 bool fwd01_eligible(int L, const int* w, const int* wp);
 size_t fwd01_img_bytes();
 void launch_fwd01_img(const float* th, int64_t offW0, int64_t offW1, int obs, const unsigned* am_w0,

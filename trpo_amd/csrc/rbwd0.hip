@@ -145,8 +145,8 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
   constexpr int TM = kR0TM, CT = kR0CT;
 
   const int tid0 = threadIdx.x;
-  const int r0 = blockIdx.x * A.rows_per_split;
-  const int r1 = min(A.rows, r0 + A.rows_per_split);
+  const int r0 = blockIdx.x * A.dst.rows_per_split;
+  const int r1 = min(A.rows, r0 + A.dst.rows_per_split);
   const int wv = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   const int Npad = A.Npad, lda = A.lda, K = A.K;
   constexpr int kOob = 0x40000000;
@@ -547,7 +547,7 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
 
   // ---- this split's slab: W_0 block [obs][N] and the bias colsum ----
   const int lane = tid0 & 63, lr = lane & 31, lh = lane >> 5, col0 = 32 * CT * (tid0 >> 6);
-  float* out = A.slab + (size_t)blockIdx.x * A.slab_stride;
+  float* out = A.dst.slab + (size_t)blockIdx.x * A.dst.slab_stride;
   const float fG = Eacc == (1 << 20) ? 0.0f : __builtin_ldexpf(1.0f, -(eX + Eacc));
 #pragma unroll
   for (int tn = 0; tn < CT; ++tn) {
@@ -558,11 +558,11 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int i = 32 * ot + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (i < A.obs) out[A.off_w + (int64_t)i * A.N + j] = G[ot][tn][r] * fG;
+          if (i < A.obs) out[A.dst.off_w + (int64_t)i * A.N + j] = G[ot][tn][r] * fG;
         }
     }
     const float bt = xadd_f<true>(bsum[tn]);   // the two lane halves' rows, same order on both
-    if (lh == 0 && j < A.N) out[A.off_b + j] = bt;
+    if (lh == 0 && j < A.N) out[A.dst.off_b + j] = bt;
   }
 }
 
@@ -596,13 +596,13 @@ bool rbwd0_eligible(int obs_pad, int x_ldp, int hid_pad, int K) {
 }
 
 void launch_rbwd0(const RBwd0Args& a, hipStream_t s) {
-  if (a.splits <= 0) return;
+  if (a.dst.splits <= 0) return;
   if (!rbwd0_eligible(a.obs, a.x_ldp, a.Npad, a.K) || a.obs > 128 || !a.Xh || !a.Xl || !a.eX || !a.H ||
       (a.nseg > 1 && (!a.A1 || !a.B1)) || (a.E && !a.RH) || a.ldk < (a.K + 15) / 16 * 16 || a.lda < a.K)
     throw std::runtime_error("rbwd0: unsupported shape or missing operand");
   if ((int64_t)a.x_ldp * a.x_mpad * 2 >= (int64_t(1) << 32) || (int64_t)kR0Rows * a.lda * 4 >= (int64_t(1) << 31))
     throw std::runtime_error("rbwd0: operand beyond the buffer-descriptor range");
-  if ((int64_t)a.splits * a.rows_per_split < a.rows) throw std::runtime_error("rbwd0: splits do not cover the rows");
+  if ((int64_t)a.dst.splits * a.dst.rows_per_split < a.rows) throw std::runtime_error("rbwd0: splits do not cover the rows");
   if (a.nseg != 1 && a.nseg != 2) throw std::runtime_error("rbwd0: nseg must be 1 or 2");
   if ((a.nseg == 2) != (a.E != nullptr)) throw std::runtime_error("rbwd0: the E RH term goes with two segments");
   RBwd0Args b = a;
@@ -613,8 +613,8 @@ void launch_rbwd0(const RBwd0Args& a, hipStream_t s) {
     b.am_a1 = b.am_a0;
     b.am_b1 = b.am_b0;
   }
-  if (a.nseg == 2) hipLaunchKernelGGL(rbwd0_kernel<2>, dim3(a.splits), dim3(kR0NT), 0, s, b);
-  else hipLaunchKernelGGL(rbwd0_kernel<1>, dim3(a.splits), dim3(kR0NT), 0, s, b);
+  if (a.nseg == 2) hipLaunchKernelGGL(rbwd0_kernel<2>, dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
+  else hipLaunchKernelGGL(rbwd0_kernel<1>, dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
 }
 
 }  // namespace trpo

@@ -715,7 +715,7 @@ void launch_rfwd01(const Rfwd01Args& a, int num_cus, hipStream_t s) {
   if (a.n <= 0) return;
   if (a.obs < 1 || a.obs > 128 || a.ldh != 256 || a.ldz != 256)
     throw std::runtime_error("rfwd01: unsupported shape");
-  if ((int64_t)4 * a.x_mpad * 64 >= ((int64_t)1 << 31) || a.x_mpad < (a.n + kRfTile - 1) / kRfTile * kRfTile)
+  if (!rfwd01_rows_ok(a.x_mpad) || a.x_mpad < (a.n + kRfTile - 1) / kRfTile * kRfTile)
     throw std::runtime_error("rfwd01: X plane geometry");
   const int64_t ntiles = (a.n + kRfTile - 1) / kRfTile;
   const int grid = (int)std::min<int64_t>(ntiles, (int64_t)num_cus);
@@ -735,7 +735,7 @@ void launch_fwd01_img(const float* th, int64_t offW0, int64_t offW1, int obs, co
 void launch_fwd01(const Fwd01Args& a, int num_cus, hipStream_t s) {
   if (a.n <= 0) return;
   if (a.obs < 1 || a.obs > 128) throw std::runtime_error("fwd01: unsupported shape");
-  if ((int64_t)4 * a.x_mpad * 64 >= ((int64_t)1 << 31) || a.x_mpad < (a.n + kRfTile - 1) / kRfTile * kRfTile)
+  if (!rfwd01_rows_ok(a.x_mpad) || a.x_mpad < (a.n + kRfTile - 1) / kRfTile * kRfTile)
     throw std::runtime_error("fwd01: X plane geometry");
   const int64_t ntiles = (a.n + kRfTile - 1) / kRfTile;
   const int grid = (int)std::min<int64_t>(ntiles, (int64_t)num_cus);

@@ -127,8 +127,8 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
   const int apad = A.apad, bpad = A.bpad, b = A.b;
-  const int r0 = blockIdx.x * A.rows_per_split;
-  const int r1 = min(A.rows, r0 + A.rows_per_split);
+  const int r0 = blockIdx.x * A.dst.rows_per_split;
+  const int r1 = min(A.rows, r0 + A.dst.rows_per_split);
   const int col0 = 32 * w;                    // this wave's hidden columns [col0, col0 + 32)
   const bool wv = col0 < apad;
 
@@ -410,12 +410,12 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
   }
 
   // ---- this split's slab: W part [a][b] and the bias colsum ----
-  float* out = A.slab + (size_t)blockIdx.x * A.slab_stride;
+  float* out = A.dst.slab + (size_t)blockIdx.x * A.dst.slab_stride;
   if (lr < b) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int mrow = col0 + (i & 3) + 8 * (i >> 2) + 4 * lh;
-      if (mrow < A.a) out[A.off_w + (int64_t)mrow * b + lr] = G[i];
+      if (mrow < A.a) out[A.dst.off_w + (int64_t)mrow * b + lr] = G[i];
     }
   }
   sBias[w][lane] = bsum;
@@ -427,7 +427,7 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
     float t = 0.0f;
 #pragma unroll
     for (int q = 0; q < NW; ++q) t += sBias[q][tid] + sBias[q][tid + 32];
-    out[A.off_b + tid] = t;
+    out[A.dst.off_b + tid] = t;
   }
   if (tid == 0 && A.am_out) {
     float mm = 0.0f;
@@ -466,9 +466,9 @@ void launch_tail_pack(const TailPackArgs& p, hipStream_t s) {
 void launch_fvp_tail(const TailArgs& a, hipStream_t s) {
   if (!tail_eligible(a.apad, a.bpad) || a.b > 32 || a.a > a.apad)
     throw std::runtime_error("fvp_tail: unsupported layer shape");
-  if (a.splits <= 0) return;
-  if (a.rows_per_split % TR) throw std::runtime_error("fvp_tail: rows_per_split % 32");
-  hipLaunchKernelGGL(fvp_tail_kernel, dim3(a.splits), dim3(NW * 64), 0, s, a);
+  if (a.dst.splits <= 0) return;
+  if (a.dst.rows_per_split % TR) throw std::runtime_error("fvp_tail: rows_per_split % 32");
+  hipLaunchKernelGGL(fvp_tail_kernel, dim3(a.dst.splits), dim3(NW * 64), 0, s, a);
 }
 
 }  // namespace trpo

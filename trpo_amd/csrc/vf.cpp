@@ -199,12 +199,7 @@ struct trpo_vf {
     a.nseg = 1;
     a.seg[0] = WSeg{A, B, Mpad, Npad};
     a.colsum_seg = 0;
-    a.splits = active_splits;
-    a.rows_per_split = rows_per_split;
-    a.slab = slab;
-    a.slab_stride = slab_stride;
-    a.off_w = offw;
-    a.off_b = offb;
+    a.dst = SlabDst{active_splits, rows_per_split, slab, slab_stride, offw, offb};
     launch_wgrad(a, stream);
     check_launch();
   }
