@@ -161,8 +161,11 @@ int trpo_get_advantage_estimator(trpo_engine* e, int* kind, double* lambda);
 /* tail_values [n] f64 of the current feed: V(s_T) of paths that were cut off rather than terminated, read
  * only at path-end rows; NULL clears them.  trpo_set_batch, trpo_set_rewards and trpo_rollout_to_batch
  * clear them too.  Only TRPO_ADV_GAE uses them: computing advantages under TRPO_ADV_RETURNS while they
- * are set fails with TRPO_ERR_STATE. */
+ * are set fails with TRPO_ERR_STATE.  Called with the engine's own buffer (trpo_get_tail_view's tail,
+ * TRPO_MEM_DEVICE) it marks the values written there as set, without a copy. */
 int trpo_set_tail_values(trpo_engine* e, const double* tail_values, int mem);
+/* the feed's tail values [n] f64 as the scan will read them: zeros when none are set */
+int trpo_get_tail_values(trpo_engine* e, double* out, int mem);
 
 /* ---- the graph outputs ---------------------------------------------------- */
 /* session.run(self.losses) -> [surr, kl, ent] at the current parameters (trpo_inksci.py:53,156) */
@@ -280,7 +283,12 @@ int trpo_profile_reset(trpo_engine* e);
  * restated in float64; gym is not vendored) run on the GPU, one wave each, under the engine's
  * current policy.  Every environment collects whole episodes until its own step count reaches
  * ceil(n_timesteps / n_envs) -- utils.py:23-44's stopping rule per environment (n_envs = 1 is the
- * reference's loop) -- and the episodes are concatenated in environment order. */
+ * reference's loop) -- and the episodes are concatenated in environment order.
+ * The reference does not tell a path the environment terminated from one that time_limit or
+ * max_pathlength cut off.  The rollout records it per path, with the state s_T after the last step and
+ * the policy's distribution there (trpo_rollout_fetch_ends), so that GAE can bootstrap cut-off paths
+ * from V(s_T) (trpo_get_tail_view, trpo_vf_predict_tails).  The per-step outputs and the random
+ * draws do not depend on it. */
 typedef struct trpo_rollout_params {
   int n_envs;                /* parallel environments (1) */
   int max_pathlength;        /* config["max_steps"] = 1000 (trpo_inksci.py:17; utils.py:28) */
@@ -303,6 +311,15 @@ int trpo_rollout_cartpole(trpo_engine* e, const trpo_rollout_params* p, int64_t*
  * cat_sample uniform of every step; any may be NULL */
 int trpo_rollout_fetch(trpo_engine* e, double* obs, float* obs32, int64_t* actions, float* action_dists,
                        double* rewards, uint8_t* episode_starts, double* uniforms, int mem);
+/* How each of the rollout's n_paths paths ended, in the order of the concatenated rollout: truncated
+ * [n_paths] u8 (1 = the path's last step did not terminate the environment: time_limit or
+ * max_pathlength cut it off; a step that terminates and reaches the limit counts as terminated),
+ * final_obs [n_paths][obs_dim] f64 (s_T, the state after the last step), final_dists [n_paths][A] f32
+ * (the policy at float32(s_T) for cut-off paths, zeros for terminated ones), lengths [n_paths] i64 (T)
+ * and end_rows [n_paths] i64 (the row of the path's last step); any may be NULL.  TRPO_ERR_STATE
+ * when there is no rollout. */
+int trpo_rollout_fetch_ends(trpo_engine* e, uint8_t* truncated, double* final_obs, float* final_dists,
+                            int64_t* lengths, int64_t* end_rows, int mem);
 /* the rollout becomes the feed on the device (trpo_inksci.py:108-112,119-122): states, actions,
  * oldaction_dist, rewards and path starts, with no host round trip; baseline cleared */
 int trpo_rollout_to_batch(trpo_engine* e, int64_t n_global);
@@ -320,6 +337,22 @@ typedef struct trpo_feed_view {
   double* baseline;          /* [n] f64; trpo_set_baseline(e, view.baseline, TRPO_MEM_DEVICE) marks it set */
 } trpo_feed_view;
 int trpo_get_feed_view(trpo_engine* e, trpo_feed_view* out);
+/* The companion view of the feed's path ends, for the consumer that computes V(s_T) on the device (the
+ * VF: trpo_vf_predict_tails).  Valid only while the feed is the one trpo_rollout_to_batch loaded:
+ * after trpo_set_batch, trpo_set_rewards or a new rollout it fails with TRPO_ERR_STATE.  Zero-fills the
+ * engine's tail buffer, leaves the feed without tail values and synchronises the engine stream;
+ * trpo_set_tail_values(e, view.tail, TRPO_MEM_DEVICE) then marks the buffer set without a copy. */
+typedef struct trpo_tail_view {
+  int64_t n, n_paths;
+  int obs_dim, n_actions;
+  const float* final_obs32;  /* [n_paths][obs_dim] float32(s_T) */
+  const float* final_dist;   /* [n_paths][n_actions] f32 */
+  const int64_t* lengths;    /* [n_paths] T */
+  const uint8_t* truncated;  /* [n_paths] */
+  const int64_t* end_rows;   /* [n_paths] */
+  double* tail;              /* [n] f64, the engine's tail values */
+} trpo_tail_view;
+int trpo_get_tail_view(trpo_engine* e, trpo_tail_view* out);
 /* set only the baseline [n] f64 of the current feed (VF.predict output, trpo_inksci.py:103) */
 int trpo_set_baseline(trpo_engine* e, const double* baseline, int mem);
 /* explained_variance(baseline, returns) (utils.py:208-211, trpo_inksci.py:167) over the current
@@ -375,6 +408,11 @@ int trpo_vf_fit(trpo_vf* vf, int steps);
 int trpo_vf_gradient(trpo_vf* vf, float* grad_out, double* loss_out, int mem);
 /* VF.predict: net on the current features -> out [n] (TRPO_F32 / TRPO_F64) */
 int trpo_vf_predict(trpo_vf* vf, void* out, int dtype, int mem);
+/* V(s_T) of an engine feed's cut-off paths (trpo_get_tail_view): the features of s_T,
+ * [final_obs32 | final_dist | float32(T/10.0)] (row t = T of VF._features), one row per path, through
+ * the net; then view.tail[end_rows[p]] = truncated[p] ? (double)net[p] : 0.  Afterwards the VF's features
+ * are these n_paths rows.  Synchronises the VF's stream; n_paths = 0 succeeds. */
+int trpo_vf_predict_tails(trpo_vf* vf, const trpo_tail_view* view);
 /* multi-GPU: shard rows, all-reduce the [P] gradient (RCCL), or the host test transport */
 int trpo_vf_comm_init(trpo_vf* vf, const uint8_t id[128], int rank, int world);
 int trpo_vf_comm_set_host_allreduce(trpo_vf* vf, trpo_allreduce_cb cb, void* ctx, int rank, int world);

@@ -55,6 +55,12 @@ class FeedView(ctypes.Structure):
                 ("episode_starts", c_void_p), ("returns", c_void_p), ("baseline", c_void_p)]
 
 
+class TailView(ctypes.Structure):
+    _fields_ = [("n", c_int64), ("n_paths", c_int64), ("obs_dim", c_int), ("n_actions", c_int),
+                ("final_obs32", c_void_p), ("final_dist", c_void_p), ("lengths", c_void_p),
+                ("truncated", c_void_p), ("end_rows", c_void_p), ("tail", c_void_p)]
+
+
 FAX_CB = CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p)
 ALLREDUCE_CB = CFUNCTYPE(c_int, c_void_p, c_int64, c_int, c_void_p)
 F32, F64 = 0, 1
@@ -81,6 +87,7 @@ SIGNATURES = {
     "trpo_set_advantage_estimator": (c_int, [c_void_p, c_int, c_double]),
     "trpo_get_advantage_estimator": (c_int, [c_void_p, POINTER(c_int), POINTER(c_double)]),
     "trpo_set_tail_values": (c_int, [c_void_p, c_void_p, c_int]),
+    "trpo_get_tail_values": (c_int, [c_void_p, c_void_p, c_int]),
     "trpo_losses": (c_int, [c_void_p, POINTER(c_float)]),
     "trpo_eval_losses": (c_int, [c_void_p, c_void_p, POINTER(c_float), c_int]),
     "trpo_action_dist": (c_int, [c_void_p, c_void_p, c_int]),
@@ -106,6 +113,9 @@ SIGNATURES = {
     "trpo_rollout_cartpole": (c_int, [c_void_p, POINTER(RolloutParams), POINTER(c_int64), POINTER(c_int64)]),
     "trpo_rollout_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int]),
+    "trpo_rollout_fetch_ends": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "trpo_get_tail_view": (c_int, [c_void_p, POINTER(TailView)]),
+    "trpo_vf_predict_tails": (c_int, [c_void_p, POINTER(TailView)]),
     "trpo_set_baseline": (c_int, [c_void_p, c_void_p, c_int]),
     "trpo_get_feed_view": (c_int, [c_void_p, POINTER(FeedView)]),
     "trpo_vf_set_features_view": (c_int, [c_void_p, POINTER(FeedView), c_int]),

@@ -22,7 +22,9 @@ For the update methods, paths come in as the reference's dicts
 ``config["gae_lambda"]`` (not in the reference) switches the advantages of all three
 from ``discount(rewards) - baseline`` to GAE(lambda); paths may then carry a
 ``"tail_value"`` scalar, V(s_T) of a path that was cut off rather than terminated.
-learn() keeps CartPole-v0's time limit as a termination, as the reference does.
+learn() keeps CartPole-v0's time limit as a termination, as the reference does, unless
+``config["bootstrap_truncated"]`` is true (it needs ``gae_lambda``): the rollout then tells cut-off paths from
+terminated ones, and from the VF's first fit on the scan bootstraps every cut-off path from V(s_T).
 """
 from __future__ import annotations
 
@@ -40,7 +42,8 @@ from .utils import (EngineLoss, GetFlat, KLFirstFixedGVP, SetFromFlat, Surrogate
 CONFIG = {"max_steps": 1000, "episodes_per_roll": 1000, "gamma": 0.95, "cg_damping": 0.1,
           "max_kl": 0.01}   # trpo_inksci.py:17
 # An optional "gae_lambda" key (absent or None here: the reference's discount(rewards) - baseline) selects
-# GAE(lambda) advantages on the engine, with the VF's baseline as V.
+# GAE(lambda) advantages on the engine, with the VF's baseline as V.  With it, an optional
+# "bootstrap_truncated": True makes learn() bootstrap paths cut off by the time limit or max_steps from V(s_T).
 
 
 class Session:
@@ -115,6 +118,10 @@ class TRPOAgent:
                  device: int = 0, theta: Optional[np.ndarray] = None, config: Optional[dict] = None,
                  reinit_policy: bool = True):
         self.config = dict(CONFIG if config is None else config)
+        self.bootstrap_truncated = bool(self.config.get("bootstrap_truncated", False))
+        if self.bootstrap_truncated and self.config.get("gae_lambda") is None:
+            raise ValueError("config['bootstrap_truncated'] needs config['gae_lambda']: the reference's "
+                             "returns - baseline estimator takes no tail values")
         self.engine = Engine(obs_dim, hidden, n_actions, max_rows, device)
         self.session = Session(self.engine, reinit_policy=reinit_policy)
         self.gf = GetFlat(self.session)                          # trpo_inksci.py:71
@@ -226,7 +233,8 @@ class TRPOAgent:
         draws(i) -> (reset_uniforms, action_uniforms, max_episodes_per_env) injects the random draws
         of iteration i's rollout (env.reset and cat_sample; tests), else a Philox stream per iteration.
         record=True also returns each iteration's rollout arrays, baselines, returns and
-        standardised advantages (host copies; parity tests).
+        standardised advantages, and how its paths ended ("ends", Engine.rollout_fetch_ends) with the
+        feed's "tail_values" (zeros unless config["bootstrap_truncated"] set some) (host copies; parity tests).
         Returns one stats dict per iteration."""
         cfg = self.config
         eng = self.engine
@@ -258,6 +266,10 @@ class TRPOAgent:
             have_base = self.vf.predict_engine(eng)                                      # :103
             if record:
                 rb = self.vf.net.predict(np.empty(n, np.float64)) if have_base else np.zeros(n)
+            if self.bootstrap_truncated:
+                self.vf.predict_tails_engine(eng)   # V(s_T) of the cut-off paths; none before the first fit
+            if record:
+                r_tail = eng.tail_values()
                 r_ret, r_adv = np.empty(n), np.empty(n)
                 eng.compute_advantages_device(cfg["gamma"], returns_out=r_ret, advant_out=r_adv)
             else:
@@ -271,7 +283,8 @@ class TRPOAgent:
             rec = {"iteration": i, "steps": n, "paths": n_paths, "train": self.train,
                    "reward_mean": float(reward_mean), "end_count": self.end_count}
             if record:
-                rec.update({"rollout": eng.rollout_fetch(), "baseline": rb, "returns": r_ret, "advantages": r_adv})
+                rec.update({"rollout": eng.rollout_fetch(), "baseline": rb, "returns": r_ret, "advantages": r_adv,
+                            "ends": eng.rollout_fetch_ends(), "tail_values": r_tail})
             if reward_mean > 1.1 * 500:                                                  # :135-136
                 self.train = False
             rec["train"] = self.train                    # whether this iteration updates the policy

@@ -302,10 +302,21 @@ struct trpo_engine {
     int64_t *counts = nullptr, *episodes = nullptr, *offsets = nullptr;
     double *reset_u = nullptr, *act_u = nullptr;
     int64_t reset_u_n = 0, act_u_n = 0;
+    // how each path ended: per-environment path regions (n_envs * budget paths), the path offsets of the
+    // compaction, and the concatenated records the tail view hands out (trpo_rollout_to_batch fills them)
+    int64_t paths = 0;     // capacity in region paths
+    uint8_t* end_truncated = nullptr;
+    double* end_obs = nullptr;
+    float* end_dist = nullptr;
+    int64_t *end_len = nullptr, *end_row = nullptr, *path_offsets = nullptr;
+    uint8_t* cat_truncated = nullptr;
+    float *cat_obs32 = nullptr, *cat_dist = nullptr;
+    int64_t *cat_len = nullptr, *cat_rows = nullptr;
   } roll;
   RolloutArgs roll_args{};
-  int64_t roll_n = 0, roll_paths = 0, roll_maxcount = 0;
+  int64_t roll_n = 0, roll_paths = 0, roll_maxcount = 0, roll_maxpaths = 0;
   bool roll_valid = false;
+  bool feed_is_rollout = false;   // the feed is the one trpo_rollout_to_batch loaded (trpo_get_tail_view)
 
   // profiling
   bool prof = false;
@@ -661,11 +672,24 @@ struct trpo_engine {
     const int64_t env_cap = budget + ep_max - 1;
     const int64_t rows = env_cap * p.n_envs;
     REQUIRE(rows <= (int64_t(1) << 34), "rollout too large");
-    if (rows > roll.rows || p.n_envs > roll.envs) {
+    const int64_t paths = budget * p.n_envs;   // every episode has at least one step
+    feed_is_rollout = false;                   // the end records of the loaded feed are about to be overwritten
+    if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths) {
       for (void* ptr : roll.mem) HIPCHECK(hipFree(ptr));
       roll = RollBufs{};
       roll.rows = rows;
       roll.envs = p.n_envs;
+      roll.paths = paths;
+      roll.end_truncated = ralloc<uint8_t>(paths);
+      roll.end_obs = ralloc<double>((size_t)paths * 4);
+      roll.end_dist = ralloc<float>((size_t)paths * 2);
+      roll.end_len = ralloc<int64_t>(paths);
+      roll.end_row = ralloc<int64_t>(paths);
+      roll.cat_truncated = ralloc<uint8_t>(paths);
+      roll.cat_obs32 = ralloc<float>((size_t)paths * 4);
+      roll.cat_dist = ralloc<float>((size_t)paths * 2);
+      roll.cat_len = ralloc<int64_t>(paths);
+      roll.cat_rows = ralloc<int64_t>(paths);
       roll.obs = ralloc<double>((size_t)rows * 4);
       roll.actions = ralloc<int64_t>(rows);
       roll.dist = ralloc<float>((size_t)rows * 2);
@@ -674,7 +698,7 @@ struct trpo_engine {
       roll.uniforms = ralloc<double>(rows);
       roll.counts = ralloc<int64_t>(p.n_envs);
       roll.episodes = ralloc<int64_t>(p.n_envs);
-      roll.offsets = ralloc<int64_t>(p.n_envs);
+      roll.offsets = ralloc<int64_t>((size_t)2 * p.n_envs);
     }
     RolloutArgs a{};
     a.ps = policy_shape();
@@ -715,30 +739,39 @@ struct trpo_engine {
     a.uniforms_out = roll.uniforms;
     a.counts = roll.counts;
     a.episodes = roll.episodes;
+    a.end_truncated = roll.end_truncated;
+    a.end_obs = roll.end_obs;
+    a.end_dist = roll.end_dist;
+    a.end_len = roll.end_len;
+    a.end_row = roll.end_row;
     launch_rollout(a, stream);
     check_launch();
-    std::vector<int64_t> counts(p.n_envs), offs(p.n_envs);
+    // row offsets [n_envs], then path offsets [n_envs]: one upload
+    std::vector<int64_t> counts(p.n_envs), eps(p.n_envs), offs((size_t)2 * p.n_envs);
     copy_out(counts.data(), roll.counts, counts.size() * sizeof(int64_t), TRPO_MEM_HOST);
-    int64_t tot = 0, mx = 0;
+    copy_out(eps.data(), roll.episodes, eps.size() * sizeof(int64_t), TRPO_MEM_HOST);
+    int64_t tot = 0, mx = 0, ptot = 0, pmx = 0;
     for (int i = 0; i < p.n_envs; ++i) {
       offs[i] = tot;
       tot += counts[i];
       mx = std::max(mx, counts[i]);
+      offs[p.n_envs + i] = ptot;
+      ptot += eps[i];
+      pmx = std::max(pmx, eps[i]);
     }
     copy_in(roll.offsets, offs.data(), offs.size() * sizeof(int64_t), TRPO_MEM_HOST);
-    std::vector<int64_t> eps(p.n_envs);
-    copy_out(eps.data(), roll.episodes, eps.size() * sizeof(int64_t), TRPO_MEM_HOST);
+    roll.path_offsets = roll.offsets + p.n_envs;
     roll_args = a;
     roll_n = tot;
     roll_maxcount = mx;
-    roll_paths = 0;
-    for (int64_t x : eps) roll_paths += x;
+    roll_paths = ptot;
+    roll_maxpaths = pmx;
     roll_valid = true;
   }
 
   void rollout_compact(const RolloutOut& o) {
     REQUIRE(roll_valid, "no rollout to fetch");
-    launch_rollout_compact(roll_args, roll.offsets, o, roll_maxcount, stream);
+    launch_rollout_compact(roll_args, roll.offsets, o, o.ends_only ? roll_maxpaths : roll_maxcount, stream);
     check_launch();
   }
 
@@ -2218,6 +2251,7 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
     e->cache.batch_changed();
     e->have_rewards = false;
     e->have_tail = false;
+    e->feed_is_rollout = false;
   });
 }
 
@@ -2234,6 +2268,7 @@ int trpo_set_rewards(trpo_engine* e, const double* rewards, const uint8_t* start
     e->have_rewards = true;
     e->cache.rewards_changed();
     e->have_tail = false;
+    e->feed_is_rollout = false;
   });
 }
 
@@ -2265,8 +2300,25 @@ int trpo_set_tail_values(trpo_engine* e, const double* tail_values, int mem) {
     e->require_batch();
     e->use();
     if (!e->tail) e->tail = e->dalloc<double>(e->cap);
-    e->copy_in(e->tail, tail_values, (size_t)e->n * sizeof(double), mem);
+    // the engine's own buffer (trpo_get_tail_view's tail, written in place) is marked set without a copy
+    if (tail_values != e->tail) e->copy_in(e->tail, tail_values, (size_t)e->n * sizeof(double), mem);
     e->have_tail = true;
+  });
+}
+
+int trpo_get_tail_values(trpo_engine* e, double* out, int mem) {
+  return guarded([&] {
+    REQUIRE(e && out, "NULL argument");
+    e->require_batch();
+    e->use();
+    if (e->have_tail) {
+      e->copy_out(out, e->tail, (size_t)e->n * sizeof(double), mem);
+    } else if (mem == TRPO_MEM_DEVICE) {
+      HIPCHECK(hipMemsetAsync(out, 0, (size_t)e->n * sizeof(double), e->stream));
+      HIPCHECK(hipStreamSynchronize(e->stream));
+    } else {
+      std::fill(out, out + e->n, 0.0);
+    }
   });
 }
 
@@ -2560,7 +2612,15 @@ int trpo_rollout_to_batch(trpo_engine* e, int64_t n_global) {
     o.act32 = e->act;
     o.rewards = e->rewards;
     o.starts = e->starts;
+    // the paths' end records, for trpo_get_tail_view
+    o.path_offsets = e->roll.path_offsets;
+    o.end_truncated = e->roll.cat_truncated;
+    o.end_obs32 = e->roll.cat_obs32;
+    o.end_dist = e->roll.cat_dist;
+    o.end_len = e->roll.cat_len;
+    o.end_rows = e->roll.cat_rows;
     e->rollout_compact(o);
+    e->feed_is_rollout = true;
     e->n = N;
     e->n_global = n_global;
     e->update_x_amax();
@@ -2590,6 +2650,52 @@ int trpo_get_feed_view(trpo_engine* e, trpo_feed_view* v) {
     v->episode_starts = e->have_rewards ? e->starts : nullptr;
     v->returns = e->cache.have_returns ? e->returns : nullptr;   // stale until the advantages are computed
     v->baseline = e->baseline;
+  });
+}
+
+int trpo_rollout_fetch_ends(trpo_engine* e, uint8_t* truncated, double* final_obs, float* final_dists,
+                            int64_t* lengths, int64_t* end_rows, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
+    e->use();
+    const int64_t P = e->roll_paths;
+    const int obs_dim = e->w[0], A = e->w[e->L];
+    RolloutOut o{};
+    Staging st(mem, e->stream);
+    o.ends_only = 1;
+    o.path_offsets = e->roll.path_offsets;
+    o.end_truncated = st.out(truncated, (size_t)P);
+    o.end_obs64 = st.out(final_obs, (size_t)P * obs_dim);
+    o.end_dist = st.out(final_dists, (size_t)P * A);
+    o.end_len = st.out(lengths, (size_t)P);
+    o.end_rows = st.out(end_rows, (size_t)P);
+    e->rollout_compact(o);
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int trpo_get_tail_view(trpo_engine* e, trpo_tail_view* v) {
+  return guarded([&] {
+    REQUIRE(e && v, "NULL argument");
+    if (!(e->feed_is_rollout && e->roll_valid && e->n > 0))
+      throw std::runtime_error("the feed is not the one trpo_rollout_to_batch loaded");
+    e->use();
+    if (!e->tail) e->tail = e->dalloc<double>(e->cap);
+    HIPCHECK(hipMemsetAsync(e->tail, 0, (size_t)e->n * sizeof(double), e->stream));
+    e->have_tail = false;
+    HIPCHECK(hipStreamSynchronize(e->stream));   // other streams read and write these buffers next
+    v->n = e->n;
+    v->n_paths = e->roll_paths;
+    v->obs_dim = e->w[0];
+    v->n_actions = e->w[e->L];
+    v->final_obs32 = e->roll.cat_obs32;
+    v->final_dist = e->roll.cat_dist;
+    v->lengths = e->roll.cat_len;
+    v->truncated = e->roll.cat_truncated;
+    v->end_rows = e->roll.cat_rows;
+    v->tail = e->tail;
   });
 }
 

@@ -691,6 +691,13 @@ size_t vf_pos_workspace_bytes(int64_t n);
 void launch_vf_features(const float* obs, int obs_dim, int ld_obs, const float* dist, int A, int ld_dist,
                         const uint8_t* starts, int64_t n, int64_t* lastpos, void* ws, float* feat, int Fp,
                         hipStream_t s);
+// feat [n_paths][Fp] = [final_obs | final_dist | f32(T/10)]: the features of s_T, the state after a path's
+// T steps (row t = T of launch_vf_features)
+void launch_vf_tail_features(const float* obs, int obs_dim, const float* dist, int A, const int64_t* lengths,
+                             int64_t n_paths, float* feat, int Fp, hipStream_t s);
+// tail[end_rows[p]] = truncated[p] ? (double)pred[p] : 0.0; rows outside [0, n) are skipped
+void launch_vf_tail_scatter(const float* pred, const uint8_t* truncated, const int64_t* end_rows, int64_t n_paths,
+                            int64_t n, double* tail, hipStream_t s);
 struct VFPackArgs {
   int F, H1, H2, H1p, H2p;
   int64_t offW1, offW2;   // flat offsets of W1 [F][H1], W2 [H1][H2]
@@ -748,6 +755,12 @@ struct RolloutArgs {
   double* uniforms_out;     // optional: the cat_sample uniform of every step
   int64_t* counts;          // [n_envs] steps collected
   int64_t* episodes;        // [n_envs] episodes collected
+  // per-environment path regions (path = env * budget + episode; an environment starts at most budget episodes)
+  uint8_t* end_truncated;   // 1: the path was cut off (time limit / max_pathlength), 0: the environment terminated
+  double* end_obs;          // [.][obs_dim] s_T, the state after the path's last step
+  float* end_dist;          // [.][A] the policy's distribution at s_T of a cut-off path, zeros otherwise
+  int64_t* end_len;         // T, the path's step count
+  int64_t* end_row;         // the path's last row within its environment's step region
 };
 struct RolloutOut {         // concatenated outputs; any pointer may be NULL
   double* obs64;            // [N][obs_dim]
@@ -761,6 +774,16 @@ struct RolloutOut {         // concatenated outputs; any pointer may be NULL
   double* rewards;
   uint8_t* starts;
   double* uniforms;
+  // the per-path end records [n_paths], in the order of the concatenated rollout; written when path_offsets
+  // ([n_envs] exclusive sums of the episode counts) is given
+  const int64_t* path_offsets;
+  int ends_only;            // 1: skip the per-step pass
+  uint8_t* end_truncated;
+  double* end_obs64;        // [n_paths][obs_dim]
+  float* end_obs32;
+  float* end_dist;          // [n_paths][A]
+  int64_t* end_len;
+  int64_t* end_rows;        // index of the path's last step in the concatenated rollout
 };
 size_t rollout_lds_bytes(int maxw);
 void launch_rollout(const RolloutArgs& a, hipStream_t s);

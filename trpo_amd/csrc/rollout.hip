@@ -23,6 +23,17 @@
 // exactly utils.py:23-44 and for any n_envs every started episode completes.
 // Episodes land in a per-environment region; a compaction kernel concatenates
 // the regions in environment order (deterministic for a given seed).
+//
+// The reference scores every path end alike.  Here each path also records how it
+// ended, in a per-environment path region (an environment starts at most
+// ceil(n_timesteps / n_envs) episodes): whether it was cut off -- its last step
+// did not terminate the environment, the time limit or max_pathlength ended it --
+// or terminated (a step that does both is a termination), the state s_T after the
+// last step, T, the path's last row and, for a cut-off path, the policy's
+// distribution at s_T from one more forward that draws no uniform.  The
+// compaction kernel concatenates these records too, so that GAE can bootstrap the
+// cut-off paths from V(s_T) (vf.hip: the VF's features are [obs | dist | t/10]).
+// The per-step outputs and the Philox draw indices do not depend on any of it.
 #include "common.h"
 #include "kernels.h"
 
@@ -180,6 +191,8 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
       s[i] = -0.05 + (0.05 - -0.05) * u;
     }
     ++episode;
+    bool done = false;
+    int len = 0;
     for (int t = 0; t < a.max_pathlength; ++t) {
       const int64_t row = base + count;
       // act(ob): the obs fed to the float32 state placeholder, recorded as the float64 ob
@@ -193,7 +206,7 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
       ++adraw;
       const int action = wave_choose(p, A, r, a.train, lane);
       if (lane < A) a.dist[row * A + lane] = p;
-      const bool done = cartpole_step(s, action);
+      done = cartpole_step(s, action);
       if (lane == 0) {
         a.actions[row] = action;
         a.rewards[row] = 1.0;
@@ -201,11 +214,32 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
         if (a.uniforms_out) a.uniforms_out[row] = r;
       }
       ++count;
+      len = t + 1;
       // CartPole-v0's TimeLimit(max_episode_steps=200) reports done at step 200
       if (done || t + 1 >= a.time_limit) break;
       wave_sync();
     }
     wave_sync();
+    // How the path ended.  It was cut off (truncated) when its last step did not terminate the environment:
+    // the time limit or max_pathlength ended it, and a step that does both counts as terminated.  s is s_T;
+    // a cut-off path also records the policy's distribution there, the VF's features of s_T (vf.hip).  The
+    // extra forward draws no uniform.
+    const int64_t path = (int64_t)env * a.budget + (episode - 1);
+    const bool truncated = !done;
+    float pT = 0.0f;
+    if (truncated) {
+      if (lane < obs_dim) buf0[lane] = (float)s[lane];
+      wave_sync();
+      pT = wave_policy(a.ps, a.theta, buf0, buf1, lane);
+      wave_sync();
+    }
+    if (lane < obs_dim) a.end_obs[path * obs_dim + lane] = s[lane];
+    if (lane < A) a.end_dist[path * A + lane] = pT;
+    if (lane == 0) {
+      a.end_truncated[path] = truncated ? 1 : 0;
+      a.end_len[path] = len;
+      a.end_row[path] = count - 1;
+    }
   }
   if (lane == 0) {
     a.counts[env] = count;
@@ -218,7 +252,7 @@ __global__ void __launch_bounds__(256) rollout_compact_kernel(const RolloutArgs 
                                                               RolloutOut o) {
   const int obs_dim = a.ps.w[0], A = a.ps.w[a.ps.L];
   const int env = blockIdx.y;
-  const int64_t cnt = a.counts[env], dst0 = offsets[env], src0 = (int64_t)env * a.env_cap;
+  const int64_t cnt = o.ends_only ? 0 : a.counts[env], dst0 = offsets[env], src0 = (int64_t)env * a.env_cap;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t s = src0 + i, d = dst0 + i;
     for (int c = 0; c < obs_dim; ++c) {
@@ -236,6 +270,22 @@ __global__ void __launch_bounds__(256) rollout_compact_kernel(const RolloutArgs 
     if (o.rewards) o.rewards[d] = a.rewards[s];
     if (o.starts) o.starts[d] = a.starts[s];
     if (o.uniforms && a.uniforms_out) o.uniforms[d] = a.uniforms_out[s];
+  }
+  // the per-path end records; path offsets = exclusive sums of the environments' episode counts
+  if (!o.path_offsets) return;
+  const int64_t np = a.episodes[env], pdst0 = o.path_offsets[env], psrc0 = (int64_t)env * a.budget;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = psrc0 + i, d = pdst0 + i;
+    for (int c = 0; c < obs_dim; ++c) {
+      const double v = a.end_obs[s * obs_dim + c];
+      if (o.end_obs64) o.end_obs64[d * obs_dim + c] = v;
+      if (o.end_obs32) o.end_obs32[d * obs_dim + c] = (float)v;
+    }
+    if (o.end_dist)
+      for (int c = 0; c < A; ++c) o.end_dist[d * A + c] = a.end_dist[s * A + c];
+    if (o.end_truncated) o.end_truncated[d] = a.end_truncated[s];
+    if (o.end_len) o.end_len[d] = a.end_len[s];
+    if (o.end_rows) o.end_rows[d] = dst0 + a.end_row[s];
   }
 }
 

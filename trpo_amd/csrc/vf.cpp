@@ -512,6 +512,39 @@ int trpo_vf_predict(trpo_vf* e, void* out, int dtype, int mem) {
   });
 }
 
+int trpo_vf_predict_tails(trpo_vf* e, const trpo_tail_view* v) {
+  return guarded([&] {
+    REQUIRE(e && v, "NULL argument");
+    REQUIRE(v->obs_dim >= 1 && v->n_actions >= 1 && v->obs_dim + v->n_actions + 1 == e->F,
+            "feat_dim must equal obs_dim + n_actions + 1 (utils.py:70-77)");
+    REQUIRE(v->n_paths >= 0 && v->n >= 0, "bad tail view");
+    if (v->n_paths == 0) return;
+    REQUIRE(v->final_obs32 && v->final_dist && v->lengths && v->truncated && v->end_rows && v->tail,
+            "tail view has a NULL array");
+    e->use();
+    e->set_rows(v->n_paths, v->n_paths);
+    launch_vf_tail_features(v->final_obs32, v->obs_dim, v->final_dist, v->n_actions, v->lengths, v->n_paths, e->feat,
+                            e->Fp, e->stream);
+    check_launch();
+    e->have_feat = true;
+    e->forward();
+    VFHeadArgs h{};
+    h.n = e->n;
+    h.H2 = e->H2;
+    h.H2p = e->H2p;
+    h.Z2 = e->Z2;
+    h.w3 = e->theta + e->offW3;
+    h.b3 = e->theta + e->offb3;
+    h.train = 0;
+    h.out32 = e->stage;   // [n_paths] f32, as VF.predict returns them
+    launch_vf_head(h, e->stream);
+    check_launch();
+    launch_vf_tail_scatter(e->stage, v->truncated, v->end_rows, v->n_paths, v->n, v->tail, e->stream);
+    check_launch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
 int trpo_vf_comm_init(trpo_vf* e, const uint8_t id[128], int rank, int world) {
   return guarded([&] {
     REQUIRE(e && id, "NULL argument");

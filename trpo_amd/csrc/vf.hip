@@ -108,6 +108,37 @@ __global__ void __launch_bounds__(256) features_kernel(const float* obs, int obs
   }
 }
 
+// The features of s_T, one row per path: feat[p] = [final_obs[p] | final_dist[p] | f32(T_p/10.0)]; the time
+// feature is row t = T_p of features_kernel.  Padding zero.
+__global__ void __launch_bounds__(256) tail_features_kernel(const float* obs, int obs_dim, const float* dist, int A,
+                                                            const int64_t* lengths, int64_t n_paths, float* feat,
+                                                            int Fp) {
+  const int64_t total = n_paths * Fp;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = e / Fp;
+    const int c = (int)(e - p * Fp);
+    float v = 0.0f;
+    if (c < obs_dim) {
+      v = obs[p * obs_dim + c];
+    } else if (c < obs_dim + A) {
+      v = dist[p * A + (c - obs_dim)];
+    } else if (c == obs_dim + A) {
+      v = (float)((double)lengths[p] / 10.0);
+    }
+    feat[e] = v;
+  }
+}
+
+// tail[end_rows[p]] = V(s_T) of a cut-off path, 0 of a terminated one (tail is zero elsewhere)
+__global__ void __launch_bounds__(256) tail_scatter_kernel(const float* pred, const uint8_t* truncated,
+                                                           const int64_t* end_rows, int64_t n_paths, int64_t n,
+                                                           double* tail) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_paths; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = end_rows[p];
+    if (r >= 0 && r < n) tail[r] = truncated[p] ? (double)pred[p] : 0.0;
+  }
+}
+
 __global__ void __launch_bounds__(256) vf_pack_kernel(const VFPackArgs a, const float* theta) {
   const int64_t n1 = (int64_t)a.F * a.H1, n2 = (int64_t)a.H1 * a.H2;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n1 + n2;
@@ -211,6 +242,20 @@ void launch_vf_features(const float* obs, int obs_dim, int ld_obs, const float* 
   }
   hipLaunchKernelGGL(features_kernel, dim3(grid_of(n * Fp)), dim3(256), 0, s, obs, obs_dim, ld_obs, dist, A, ld_dist,
                      starts ? lastpos : nullptr, blockpre, n, feat, Fp);
+}
+
+void launch_vf_tail_features(const float* obs, int obs_dim, const float* dist, int A, const int64_t* lengths,
+                             int64_t n_paths, float* feat, int Fp, hipStream_t s) {
+  if (n_paths <= 0) return;
+  hipLaunchKernelGGL(tail_features_kernel, dim3(grid_of(n_paths * Fp)), dim3(256), 0, s, obs, obs_dim, dist, A,
+                     lengths, n_paths, feat, Fp);
+}
+
+void launch_vf_tail_scatter(const float* pred, const uint8_t* truncated, const int64_t* end_rows, int64_t n_paths,
+                            int64_t n, double* tail, hipStream_t s) {
+  if (n_paths <= 0) return;
+  hipLaunchKernelGGL(tail_scatter_kernel, dim3(grid_of(n_paths)), dim3(256), 0, s, pred, truncated, end_rows, n_paths,
+                     n, tail);
 }
 
 void launch_vf_pack(const VFPackArgs& a, const float* theta, hipStream_t s) {

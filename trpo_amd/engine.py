@@ -189,6 +189,7 @@ class Engine:
         check(lib.trpo_set_batch(self._h, n, n_global, s.ptr, a.ptr, adv.ptr, o.ptr, mems.pop()),
               "trpo_set_batch")
         self.n, self.n_global = n, n_global
+        self._tail_ptr = None
 
     def set_rewards(self, rewards, episode_starts, baseline=None):
         n = self.n
@@ -197,6 +198,7 @@ class Engine:
                   else episode_starts, np.uint8, (n,))
         b = _Arg(baseline, np.float64, (n,)) if baseline is not None else _Arg(None, np.float64)
         check(lib.trpo_set_rewards(self._h, r.ptr, st.ptr, b.ptr, r.mem), "trpo_set_rewards")
+        self._tail_ptr = None
 
     def set_baseline(self, baseline):
         """The VF.predict baselines of the current feed (trpo_inksci.py:103), f64 [n]."""
@@ -370,6 +372,8 @@ class Engine:
         check(lib.trpo_rollout_cartpole(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
               "trpo_rollout_cartpole")
         self.rollout_steps = n.value
+        self.rollout_paths = paths.value
+        self._tail_ptr = None
         return n.value, paths.value
 
     def rollout_fetch(self, device=None):
@@ -408,11 +412,55 @@ class Engine:
                                      st.ctypes.data_as(ctypes.c_void_p), None, MEM_HOST), "trpo_rollout_fetch")
         return {"rewards": rew, "starts": st}
 
+    def rollout_fetch_ends(self):
+        """How each path of the last rollout ended, in the order of the concatenated rollout (host arrays):
+        truncated u8 [P] (1 = cut off by the time limit or max_pathlength, 0 = the environment terminated),
+        final_obs f64 [P,4] (s_T, the state after the last step), final_dists f32 [P,A] (the policy at
+        float32(s_T) for cut-off paths, zeros otherwise), lengths i64 [P] and end_rows i64 [P] (the row of
+        each path's last step)."""
+        if getattr(self, "rollout_paths", None) is None:
+            # no rollout yet: the engine reports the state error
+            check(lib.trpo_rollout_fetch_ends(self._h, None, None, None, None, None, MEM_HOST),
+                  "trpo_rollout_fetch_ends")
+        P = self.rollout_paths
+        out = {"truncated": np.empty(P, np.uint8), "final_obs": np.empty((P, self.obs_dim)),
+               "final_dists": np.empty((P, self.n_actions), np.float32), "lengths": np.empty(P, np.int64),
+               "end_rows": np.empty(P, np.int64)}
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        check(lib.trpo_rollout_fetch_ends(self._h, ptr(out["truncated"]), ptr(out["final_obs"]),
+                                          ptr(out["final_dists"]), ptr(out["lengths"]), ptr(out["end_rows"]),
+                                          MEM_HOST), "trpo_rollout_fetch_ends")
+        return out
+
+    def tail_view(self) -> "_lib.TailView":
+        """Device pointers to the path ends of the feed rollout_to_batch loaded and to the engine's tail
+        buffer, which it zero-fills (synchronises the engine stream); any other feed is a state error."""
+        v = _lib.TailView()
+        self._tail_ptr = None
+        check(lib.trpo_get_tail_view(self._h, ctypes.byref(v)), "trpo_get_tail_view")
+        self._tail_ptr = v.tail
+        return v
+
+    def set_tail_values_in_place(self):
+        """Mark the engine's own tail buffer, written through the last tail_view().tail, as the feed's tail
+        values (a fresh tail_view() would zero it, so the pointer of the last one is kept)."""
+        if getattr(self, "_tail_ptr", None) is None:
+            raise _lib.EngineError("set_tail_values_in_place: no tail_view() was taken of this feed")
+        check(lib.trpo_set_tail_values(self._h, self._tail_ptr, MEM_DEVICE), "trpo_set_tail_values")
+
+    def tail_values(self) -> np.ndarray:
+        """The feed's tail values as the GAE scan reads them, f64 [n]: zeros when none are set."""
+        out = np.empty(self.n, np.float64)
+        check(lib.trpo_get_tail_values(self._h, out.ctypes.data_as(ctypes.c_void_p), MEM_HOST),
+              "trpo_get_tail_values")
+        return out
+
     def rollout_to_batch(self, n_global: Optional[int] = None):
         """Load the rollout as the feed (states, actions, oldaction_dist, rewards, path starts) on the device."""
         N = self.rollout_steps
         check(lib.trpo_rollout_to_batch(self._h, N if n_global is None else int(n_global)), "trpo_rollout_to_batch")
         self.n, self.n_global = N, (N if n_global is None else int(n_global))
+        self._tail_ptr = None
 
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on: bool = True):

@@ -143,6 +143,13 @@ class VFNet:
         check(lib.trpo_vf_predict(self._h, ctypes.c_void_p(ptr), _lib.F64 if dtype == np.float64 else _lib.F32,
                                   MEM_DEVICE), "trpo_vf_predict")
 
+    def predict_tails(self, view):
+        """V(s_T) of the cut-off paths of an engine feed, written into the engine's tail buffer through
+        its tail view; the features become the paths' rows ``[f32(s_T) | dist(s_T) | f32(T/10)]``."""
+        check(lib.trpo_vf_predict_tails(self._h, ctypes.byref(view)), "trpo_vf_predict_tails")
+        if int(view.n_paths) > 0:
+            self.n = int(view.n_paths)
+
     def set_feature_matrix(self, feat, n_global: Optional[int] = None):
         n = int(feat.shape[0])
         f = _Arg(feat, np.float32, (n, self.feat_dim))
@@ -256,6 +263,17 @@ class VF(object):
         self.net.set_features_view(view)
         self.net.predict_to_device(view.baseline)
         engine.set_baseline_in_place()
+        return True
+
+    def predict_tails_engine(self, engine) -> bool:
+        """V(s_T) for every cut-off path of the feed the engine loaded from its rollout, set as the feed's
+        tail values in place (GAE's bootstrap).  Before the first fit the reference predicts zeros; the
+        feed then has no tail values.  Leaves the net's features on the paths' rows."""
+        if self.net is None:
+            return False
+        view = engine.tail_view()
+        self.net.predict_tails(view)
+        engine.set_tail_values_in_place()
         return True
 
     def fit_engine(self, engine):
