@@ -67,6 +67,16 @@ inline int pad4(int x) { return (x + 3) & ~3; }
 
 inline void check_launch() { HIPCHECK(hipGetLastError()); }
 
+// Split-K geometry of the weight-gradient slabs (SlabDst) for n rows over at most `splits` slabs: rows per split,
+// a multiple of the largest wgrad k-tile (32 rows) and >= 64, and the splits that then hold rows
+struct SplitGeom {
+  int rows_per_split, active;
+};
+inline SplitGeom split_geometry(int64_t n, int splits) {
+  const int64_t rps = std::max<int64_t>(64, ((n + splits - 1) / splits + 31) / 32 * 32);
+  return SplitGeom{(int)rps, (int)std::max<int64_t>(1, (n + rps - 1) / rps)};
+}
+
 // caller pointer (host or device, TRPO_MEM_*) -> device buffer on `s`; host copies are
 // synchronous so the caller may free its buffer on return
 inline void copy_in(void* dst, const void* src, size_t bytes, int mem, hipStream_t s) {

@@ -153,7 +153,7 @@ struct trpo_engine {
   unsigned* am_x() const { return f16 ? amax : nullptr; }
   unsigned* am_w(int l) const { return am(0, l); }
   unsigned* am_v(int l) const { return am(1, l); }
-  unsigned* am_wt(int l) const { return am(2, l); }
+  // group 2: the trial weights' W halves (trial_set)
   unsigned* am_d(int l) const { return am(3, l); }
   unsigned* am_ds(int l) const { return am(4, l); }
   unsigned* am_rh(int l) const { return am(5, l); }
@@ -183,15 +183,14 @@ struct trpo_engine {
   bool planes_geom_l0() const {   // layer 0's row GEMMs fit the plane kernel
     return L >= 2 && wp[1] % 256 == 0 && r16(wp[0]) % 64 == 0;
   }
-  bool planes_l0() const {
-    return x_planes && planes_geom_l0() && g_options.planes != 0 && split_on() &&
-           rowgemm_uses_split(wp[1], RowEpi::kTanh);
-  }
+  bool f16_split() const { return f16 && split_on(); }
+  bool x_planes_on() const { return x_planes && g_options.planes != 0 && split_on(); }
+  bool planes_l0() const { return x_planes_on() && planes_geom_l0() && rowgemm_uses_split(wp[1], RowEpi::kTanh); }
   // X's planes also feed the fused layer-1 R-backward + layer-0 weight gradient (rbwd0.hip)
   bool rbwd0_geom() const { return L >= 2 && rbwd0_eligible(wp[0], (wp[0] + 63) / 64 * 64, wp[1], wp[2]); }
-  // attach X's planes and the blocked copy (into `dst`) of the 2 weight planes at `w3` to a layer-0 segment
-  void attach_x_planes(GemmSeg& sg, const uint16_t* w3, uint16_t* dst) {
-    launch_block_planes(w3, 2, wp[1], r16(wp[0]), dst, stream);
+  // attach X's planes and the blocked copy (into `dst`) of the segment's 2 weight planes to a layer-0 segment
+  void attach_x_planes(GemmSeg& sg, uint16_t* dst) {
+    launch_block_planes(sg.B3, 2, wp[1], r16(wp[0]), dst, stream);
     sg.Ah = Xh;
     sg.Al = Xl;
     sg.ldp = x_ldp;
@@ -202,8 +201,7 @@ struct trpo_engine {
   uint16_t* tail_planes = nullptr;   // head planes of the fused FVP tail (tail.hip), [2][2][32][kTailK]
   // the fused last-layer tail: f16 split, last hidden width in (128, 256], 17..32 actions
   bool use_tail() const {
-    return g_options.tail != 0 && f16 && split_on() && L >= 2 &&
-           tail_eligible(wp[L - 1], wp[L]) && w[L] <= 32;
+    return g_options.tail != 0 && f16_split() && L >= 2 && tail_eligible(wp[L - 1], wp[L]) && w[L] <= 32;
   }
   // whether the FVP path reads E_{L-2} (the plain tanh'' term under the last hidden layer): every path
   // but the fused tail, which recomputes it (tail.hip)
@@ -214,12 +212,17 @@ struct trpo_engine {
       cache.prepared = false;
   }
 
-  // fused FVP chain (chain.hip): weight images in consumption order + chunk table
+  // weight images in the order a fused kernel consumes their chunks, with the chunk table
+  struct ImageSet {
+    uint16_t* img = nullptr;
+    int* tab = nullptr;
+    int* e = nullptr;   // f16 images: one scale exponent per job
+    int nchunks = 0;
+    ChainImgArgs jobs{};
+  };
+  // fused FVP chain (chain.hip)
   int chain_otm = 0;         // register tiles per hidden layer; 0 = shape not eligible
-  uint16_t* chain_img = nullptr;
-  int* chain_tab = nullptr;
-  int chain_nchunks = 0;
-  ChainImgArgs chain_jobs{};
+  ImageSet chain_set;
   // auto (option 1) takes the chain up to 8 register tiles (hidden widths <= 128), where it
   // beats the per-layer row GEMMs; at 16 tiles its per-128-state weight re-streaming
   // (~2 MB of bf16 planes per workgroup tile) costs more than the fusion saves
@@ -227,38 +230,29 @@ struct trpo_engine {
   // two hidden layers of width <= 64, obs <= 128, <= 32 actions; reuses the chain's weight images
   bool use_fused() const { return g_options.fused != 0 && chain_otm > 0 && fused_fvp_eligible(L, w.data()); }
   // the same launch on the f16 split (fused16.hip, option fused = 3): two hidden layers of width 49..64; its
-  // own weight images (2 f16 planes, one scale exponent per job in f16_e) and chunk table
-  uint16_t* f16_img = nullptr;
-  int* f16_tab = nullptr;
-  int* f16_e = nullptr;
+  // own weight images (2 f16 planes, one scale exponent per job) and chunk table
+  ImageSet f16_set;
   bool f16_v_img_ready = false;   // cg(): the V images of the next fvp_fused16 were built by the CG step launch
   unsigned* cg_ticket = nullptr;  // cg_step_slabs_kernel's arrival ticket (zero between launches)
-  int f16_nchunks = 0;
-  ChainImgArgs f16_jobs{};
   // the line-search loss forward's images (W_0 | W_1 | W_2 of the trial vector, fwd_loss16)
-  uint16_t* f16_limg = nullptr;
-  int* f16_ltab = nullptr;
-  int* f16_le = nullptr;
-  int f16_lnchunks = 0;
-  ChainImgArgs f16_ljobs{};
-  bool use_fused16() const { return g_options.fused == 3 && f16 && f16_img && fused16_eligible(L, w.data()); }
+  ImageSet f16_loss_set;
+  bool use_fused16() const { return g_options.fused == 3 && f16 && f16_set.img && fused16_eligible(L, w.data()); }
   // layer 1's R-backward (and the policy gradient's backward into layer 0) fused with layer 0's weight
   // gradient (rbwd0.hip): f16 split with X's planes, obs <= 128, first hidden width <= 256
   uint16_t* rf_img = nullptr;   // rfwd.hip's chunk image (V0^T, W1, V1 in the kernel's LDS order), per FVP
   uint16_t* fw_img = nullptr;   // rfwd.hip's forward image (W0^T, W1), per forward
   // the R-forward through layers 0 and 1 in one launch: X's planes, the fused tail (RZ2 is its pre-activation)
   bool use_rfwd01() const {
-    return g_options.rfwd01 != 0 && rf_img && f16 && split_on() && use_tail() && planes_l0() &&
+    return g_options.rfwd01 != 0 && rf_img && f16_split() && use_tail() && planes_l0() &&
            rfwd01_eligible(L, w.data(), wp.data()) && rfwd01_rows_ok(x_mpad);
   }
   // the forward's layers 0 and 1 in one launch (rfwd.hip fwd01_kernel): tanh layers of 256, X on its planes
   bool use_fwd01() const {
-    return g_options.fwd01 != 0 && fw_img && f16 && split_on() && planes_l0() && fwd01_eligible(L, w.data(), wp.data()) &&
+    return g_options.fwd01 != 0 && fw_img && f16_split() && planes_l0() && fwd01_eligible(L, w.data(), wp.data()) &&
            rfwd01_rows_ok(x_mpad);
   }
   bool use_rbwd0() const {
-    return g_options.rbwd0 != 0 && f16 && x_planes && rbwd0_geom() && g_options.planes != 0 && split_on() &&
-           rowgemm_uses_split(wp[1], RowEpi::kRBwd);
+    return g_options.rbwd0 != 0 && f16 && x_planes_on() && rbwd0_geom() && rowgemm_uses_split(wp[1], RowEpi::kRBwd);
   }
   RBwd0Args rbwd0_args(const int* skip) const {
     RBwd0Args a{};
@@ -360,7 +354,16 @@ struct trpo_engine {
     trpo_engine* e;
     int idx = -1;
     Scope(trpo_engine* eng, const char* tag) : e(eng) {
-      if (!e->prof) return;
+      if (e->prof) begin(tag);
+    }
+    // "<prefix><suffix>", and the per-layer tags "<prefix>_l<l>"
+    Scope(trpo_engine* eng, const char* prefix, const char* suffix) : e(eng) {
+      if (e->prof) begin(std::string(prefix) + suffix);
+    }
+    Scope(trpo_engine* eng, const char* prefix, int l) : e(eng) {
+      if (e->prof) begin(std::string(prefix) + "_l" + std::to_string(l));
+    }
+    void begin(const std::string& tag) {
       Ev ev{tag, e->take_event(), e->take_event()};
       HIPCHECK(hipEventRecord(ev.a, e->stream));
       e->ev_live.push_back(ev);
@@ -520,9 +523,66 @@ struct trpo_engine {
     HIPCHECK(hipStreamSynchronize(stream));
   }
 
-  // Weight-image layout of the fused FVP chain, in the order the kernel consumes
-  // chunks: R-forward F_0 (V_0), F_l (W_l, V_l) for l = 1..L-1, then R-backward
-  // B_l (W_l^T, V_l^T) for l = L-1..1.  Each segment is ceil(K/32) chunks of
+  // One image job: W_l (which = 0) or V_l (1), transposed or not, as K x O
+  struct ImgJob {
+    int l, trans, which;
+  };
+  struct ImgGeom {
+    int kc, otp, csz;   // k-chunks, padded output rows, 16-B units per chunk
+  };
+  // the order the FVP kernels consume chunks: R-forward F_0 (V_0), F_l (W_l, V_l) for l = 1..L-1, then
+  // R-backward B_l (W_l^T, V_l^T) for l = L-1..1
+  std::vector<ImgJob> fvp_image_order() const {
+    std::vector<ImgJob> order = {ImgJob{0, 0, 1}};
+    for (int l = 1; l < L; ++l) {
+      order.push_back({l, 0, 0});
+      order.push_back({l, 0, 1});
+    }
+    for (int l = L - 1; l >= 1; --l) {
+      order.push_back({l, 1, 0});
+      order.push_back({l, 1, 1});
+    }
+    return order;
+  }
+  // lay `order` out under geom(l, trans, K, O): the jobs and the chunk table, then the image, the table and
+  // n_exps scale exponents (allocated in that order), the table uploaded
+  template <class Geom>
+  void build_images(ImageSet& is, const std::vector<ImgJob>& order, int n_exps, Geom geom) {
+    REQUIRE(order.size() <= (size_t)kMaxChainJobs, "fvp chain: layout too large");
+    std::vector<int> tab;
+    int64_t off16 = 0;
+    is.jobs.n = 0;
+    for (const ImgJob& o : order) {
+      const int l = o.l, K = o.trans ? w[l + 1] : w[l], O = o.trans ? w[l] : w[l + 1];
+      const ImgGeom g = geom(l, o.trans, K, O);
+      ChainImgJob& j = is.jobs.job[is.jobs.n++];
+      j.src_off = offW[l];
+      j.dst_off = off16 * 8;
+      j.K = K;
+      j.O = O;
+      j.ldw = w[l + 1];
+      j.trans = o.trans;
+      j.kc = g.kc;
+      j.otp = g.otp;
+      j.which = o.which;
+      j.pad = 0;
+      for (int c = 0; c < g.kc; ++c) {
+        tab.push_back((int)(off16 + (int64_t)c * g.csz));
+        tab.push_back(g.csz);
+      }
+      off16 += (int64_t)g.kc * g.csz;
+    }
+    REQUIRE(off16 < (int64_t(1) << 31), "fvp chain: layout too large");
+    is.img = dalloc<uint16_t>((size_t)off16 * 8);
+    is.tab = dalloc<int>(tab.size());
+    if (n_exps) is.e = dalloc<int>(n_exps);
+    is.jobs.img = is.img;
+    HIPCHECK(hipMemcpyAsync(is.tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHECK(hipStreamSynchronize(stream));   // `tab` is a local vector
+    is.nchunks = (int)(tab.size() / 2);
+  }
+
+  // Weight images of the fused FVP chain: each segment is ceil(K/32) chunks of
   // [3 planes][16*ceil(O/16) rows][32] bf16.
   void setup_chain() {
     if (L < 2 || w[L] > 32) return;
@@ -530,46 +590,10 @@ struct trpo_engine {
     for (int l = 1; l < L; ++l) hmax = std::max(hmax, w[l]);
     const int otm = chain_max_tiles(hmax);
     if (!otm) return;
-    std::vector<int> tab;
-    int64_t off16 = 0;
-    int nj = 0;
-    auto seg = [&](int l, int trans, int which) {
-      const int K = trans ? w[l + 1] : w[l], O = trans ? w[l] : w[l + 1];
-      const int kc = (K + 31) / 32, otp = (O + 15) / 16 * 16, csz = otp * 12;   // 16-B units per chunk
-      ChainImgJob& j = chain_jobs.job[nj++];
-      j.src_off = offW[l];
-      j.dst_off = off16 * 8;
-      j.K = K;
-      j.O = O;
-      j.ldw = w[l + 1];
-      j.trans = trans;
-      j.kc = kc;
-      j.otp = otp;
-      j.which = which;
-      j.pad = 0;
-      for (int c = 0; c < kc; ++c) {
-        tab.push_back((int)(off16 + (int64_t)c * csz));
-        tab.push_back(csz);
-      }
-      off16 += (int64_t)kc * csz;
-    };
-    seg(0, 0, 1);
-    for (int l = 1; l < L; ++l) {
-      seg(l, 0, 0);
-      seg(l, 0, 1);
-    }
-    for (int l = L - 1; l >= 1; --l) {
-      seg(l, 1, 0);
-      seg(l, 1, 1);
-    }
-    REQUIRE(nj <= kMaxChainJobs && off16 < (int64_t(1) << 31), "fvp chain: layout too large");
-    chain_jobs.n = nj;
-    chain_img = dalloc<uint16_t>((size_t)off16 * 8);
-    chain_tab = dalloc<int>(tab.size());
-    chain_jobs.img = chain_img;
-    HIPCHECK(hipMemcpyAsync(chain_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHECK(hipStreamSynchronize(stream));   // `tab` is a local vector
-    chain_nchunks = (int)(tab.size() / 2);
+    build_images(chain_set, fvp_image_order(), 0, [](int, int, int K, int O) {
+      const int otp = r16(O);
+      return ImgGeom{(K + 31) / 32, otp, otp * 12};
+    });
     chain_otm = otm;
   }
 
@@ -578,64 +602,19 @@ struct trpo_engine {
   // hidden layers are 4 tiles of 16 whatever the width, the padding zeros)
   void setup_fused16() {
     if (!fused16_eligible(L, w.data())) return;
-    std::vector<int> tab;
-    int64_t off16 = 0;
-    int nj = 0;
-    ChainImgArgs* jobs = &f16_jobs;
-    auto seg = [&](int l, int trans, int which) {
-      const int K = trans ? w[l + 1] : w[l], O = trans ? w[l] : w[l + 1];
+    auto geom = [this](int l, int trans, int K, int O) {
       const bool k_hidden = trans ? l + 1 < L : l > 0, o_hidden = trans ? true : l + 1 < L;
       const int kc = l == 0 && !trans ? fused16_obs_chunks(w[0]) : k_hidden ? 2 : (K + 31) / 32;
-      const int otp = o_hidden ? 64 : (O + 15) / 16 * 16, csz = otp * 8;
-      ChainImgJob& j = jobs->job[nj++];
-      j.src_off = offW[l];
-      j.dst_off = off16 * 8;
-      j.K = K;
-      j.O = O;
-      j.ldw = w[l + 1];
-      j.trans = trans;
-      j.kc = kc;
-      j.otp = otp;
-      j.which = which;
-      j.pad = 0;
-      for (int c = 0; c < kc; ++c) {
-        tab.push_back((int)(off16 + (int64_t)c * csz));
-        tab.push_back(csz);
-      }
-      off16 += (int64_t)kc * csz;
+      const int otp = o_hidden ? 64 : r16(O);
+      return ImgGeom{kc, otp, otp * 8};
     };
-    seg(0, 0, 1);
-    for (int l = 1; l < L; ++l) {
-      seg(l, 0, 0);
-      seg(l, 0, 1);
-    }
-    for (int l = L - 1; l >= 1; --l) {
-      seg(l, 1, 0);
-      seg(l, 1, 1);
-    }
-    REQUIRE(nj == (L == 3 ? kFused16Jobs : 5), "fused16: job count");
-    f16_jobs.n = nj;
-    f16_img = dalloc<uint16_t>((size_t)off16 * 8);
-    f16_tab = dalloc<int>(tab.size());
-    f16_e = dalloc<int>(kFused16Jobs);
-    f16_jobs.img = f16_img;
-    HIPCHECK(hipMemcpyAsync(f16_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHECK(hipStreamSynchronize(stream));   // `tab` is a local vector
-    f16_nchunks = (int)(tab.size() / 2);
+    const std::vector<ImgJob> order = fvp_image_order();
+    REQUIRE((int)order.size() == (L == 3 ? kFused16Jobs : 5), "fused16: job count");
+    build_images(f16_set, order, kFused16Jobs, geom);
     // the loss forward's W_0 | W_1 | W_2 (from the trial vector: which = 0, built per line-search trial)
-    tab.clear();
-    off16 = 0;
-    nj = 0;
-    jobs = &f16_ljobs;
-    for (int l = 0; l < L; ++l) seg(l, 0, 0);
-    f16_ljobs.n = nj;
-    f16_limg = dalloc<uint16_t>((size_t)off16 * 8);
-    f16_ltab = dalloc<int>(tab.size());
-    f16_le = dalloc<int>(nj);
-    f16_ljobs.img = f16_limg;
-    HIPCHECK(hipMemcpyAsync(f16_ltab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHECK(hipStreamSynchronize(stream));
-    f16_lnchunks = (int)(tab.size() / 2);
+    std::vector<ImgJob> loss_order;
+    for (int l = 0; l < L; ++l) loss_order.push_back({l, 0, 0});
+    build_images(f16_loss_set, loss_order, L, geom);
   }
 
   PolicyShape policy_shape() const {
@@ -808,12 +787,9 @@ struct trpo_engine {
     ~PgSplits() { e->use_splits(e->S); }
   };
   void set_splits() {
-    // rows per split: a multiple of the 16-row k-tile, >= 64 rows
-    const int smax = S_cur;
-    int64_t rps = (n + smax - 1) / smax;
-    rps = std::max<int64_t>(64, (rps + 31) / 32 * 32);   // multiple of the largest wgrad k-tile
-    rows_per_split = (int)rps;
-    active_splits = (int)std::max<int64_t>(1, (n + rps - 1) / rps);
+    const SplitGeom sg = split_geometry(n, S_cur);
+    rows_per_split = sg.rows_per_split;
+    active_splits = sg.active;
   }
   int active_splits = 1;
   // where the launches that follow write layer l's weight-gradient block, under the geometry above
@@ -931,32 +907,59 @@ struct trpo_engine {
   static int r16(int k) { return (k + 15) / 16 * 16; }
   size_t plane3_f(int l) const { return (size_t)wp[l + 1] * r16(wp[l]); }   // WF part: K = wp[l], N = wp[l+1]
   size_t plane3_b(int l) const { return (size_t)wp[l] * r16(wp[l + 1]); }   // WB part: K = wp[l+1], N = wp[l]
-  SplitJob job_f(const std::vector<float*>& wf, const std::vector<uint16_t*>& wf3, int l, int part) const {
-    return SplitJob{wf[l] + (size_t)part * wp[l] * wp[l + 1], wf3[l] + part * 3 * plane3_f(l), wp[l], wp[l + 1],
-                    wp[l + 1], r16(wp[l]), part ? am_v(l) : (&wf == &WFt ? am_wt(l) : am_w(l))};
+  // A set of packed forward weights: the [W;V] matrices, their planes and the running-max group of the W halves.
+  // The current set serves theta (and the tangent in its V halves), the trial set the line search's vectors
+  // (W halves only).
+  struct WeightSet {
+    const std::vector<float*>& wf;
+    const std::vector<uint16_t*>& wf3;
+    int am_group;
+  };
+  WeightSet cur_set() const { return WeightSet{WF, WF3, 0}; }
+  WeightSet trial_set() const { return WeightSet{WFt, WFt3, 2}; }
+  unsigned* am_w(const WeightSet& ws, int l) const { return am(ws.am_group, l); }
+  enum Part { kW = 0, kV = 1 };   // the halves of a packed matrix
+  SplitJob job_f(const WeightSet& ws, int l, int part) const {
+    return SplitJob{ws.wf[l] + (size_t)part * wp[l] * wp[l + 1], ws.wf3[l] + part * 3 * plane3_f(l), wp[l], wp[l + 1],
+                    wp[l + 1], r16(wp[l]), part ? am_v(l) : am_w(ws, l)};
   }
   SplitJob job_b(int l, int part) const {
     return SplitJob{WB[l] + (size_t)part * wp[l + 1] * wp[l], WB3[l] + part * 3 * plane3_b(l), wp[l + 1], wp[l],
                     wp[l], r16(wp[l + 1]), part ? am_v(l) : am_w(l)};
   }
-  // attach the planes of a packed matrix part to a row-GEMM segment
-  static void seg3(GemmSeg& sg, uint16_t* base, size_t plane, int part, int K) {
-    sg.B3 = base + part * 3 * plane;
-    sg.ldk = r16(K);
-    sg.plane = (int)plane;
+  // Row-GEMM segments: A [n][K] (running max amaxA, NULL = bounded by 1) times a half of a packed matrix, with
+  // that half's planes and running max.  Forward: layer l's W_l / V_l of `ws`, K = wp[l]; backward: W_l^T / V_l^T,
+  // K = wp[l+1].
+  GemmSeg fwd_seg(int l, Part part, const float* A, const unsigned* amaxA, const WeightSet& ws) const {
+    GemmSeg sg{A, ws.wf[l] + (size_t)part * wp[l] * wp[l + 1], wp[l], wp[l + 1], wp[l]};
+    sg.B3 = ws.wf3[l] + part * 3 * plane3_f(l);
+    sg.ldk = r16(wp[l]);
+    sg.plane = (int)plane3_f(l);
+    sg.amaxA = amaxA;
+    sg.amaxB = part ? am_v(l) : am_w(ws, l);
+    return sg;
+  }
+  GemmSeg bwd_seg(int l, Part part, const float* A, const unsigned* amaxA) const {
+    GemmSeg sg{A, WB[l] + (size_t)part * wp[l + 1] * wp[l], wp[l + 1], wp[l], wp[l + 1]};
+    sg.B3 = WB3[l] + part * 3 * plane3_b(l);
+    sg.ldk = r16(wp[l + 1]);
+    sg.plane = (int)plane3_b(l);
+    sg.amaxA = amaxA;
+    sg.amaxB = part ? am_v(l) : am_w(l);
+    return sg;
   }
   bool split_on() const { return g_options.split_mfma != 0; }
   // split the given packed-matrix parts; only layers whose GEMM takes the split path
-  void split_parts(bool fwd_w, bool fwd_v, bool bwd_w, bool bwd_v, const std::vector<float*>& wf,
-                   const std::vector<uint16_t*>& wf3, const int* skip, const char* tag) {
+  void split_parts(bool fwd_w, bool fwd_v, bool bwd_w, bool bwd_v, const WeightSet& ws, const int* skip,
+                   const char* tag) {
     if (!split_on()) return;
     SplitArgs sa{};
     sa.f16 = f16;
     for (int l = 0; l < L; ++l) {
       const bool f = rowgemm_uses_split(wp[l + 1], RowEpi::kTanh);   // layer l's forward output
       const bool b = l >= 1 && rowgemm_uses_split(wp[l], RowEpi::kRBwd);   // backward into layer l's input
-      if (f && fwd_w) sa.job[sa.n++] = job_f(wf, wf3, l, 0);
-      if (f && fwd_v) sa.job[sa.n++] = job_f(wf, wf3, l, 1);
+      if (f && fwd_w) sa.job[sa.n++] = job_f(ws, l, 0);
+      if (f && fwd_v) sa.job[sa.n++] = job_f(ws, l, 1);
       if (b && bwd_w) sa.job[sa.n++] = job_b(l, 0);
       if (b && bwd_v) sa.job[sa.n++] = job_b(l, 1);
       if (sa.n > kMaxSplitJobs - 4 || (l == L - 1 && sa.n)) {
@@ -969,7 +972,7 @@ struct trpo_engine {
   }
   void ensure_w3() {
     if (split_on() && !cache.w3_valid) {
-      split_parts(true, false, true, false, WF, WF3, nullptr, "split_w");
+      split_parts(true, false, true, false, cur_set(), nullptr, "split_w");
       cache.w3_valid = true;
     }
   }
@@ -983,18 +986,14 @@ struct trpo_engine {
     return a;
   }
 
-  // forward through layers 0..L-1 with weights packed in wf (W half); the head
+  // forward through layers 0..L-1 with the weights of `ws` (W halves); the head
   // epilogue is `head`; hidden activations go to `hout`
-  void forward(const std::vector<float*>& wf, const std::vector<uint16_t*>& wf3, const float* th,
-               const std::vector<float*>& hout, RowEpi head, const char* tag) {
+  void forward(const WeightSet& ws, const float* th, const std::vector<float*>& hout, RowEpi head, const char* tag) {
     int l_first = 0;
     if (use_fwd01()) {   // layers 0 and 1 in one launch; H1 stored by the prepare pass only (the FVP reads it)
-      const bool wt = &wf == &WFt;
-      char t[32];
-      std::snprintf(t, sizeof t, "%s_img", tag);
       {
-        Scope sp(this, t);
-        launch_fwd01_img(th, offW[0], offW[1], w[0], wt ? am_wt(0) : am_w(0), wt ? am_wt(1) : am_w(1), fw_img, stream);
+        Scope sp(this, tag, "_img");
+        launch_fwd01_img(th, offW[0], offW[1], w[0], am_w(ws, 0), am_w(ws, 1), fw_img, stream);
         check_launch();
       }
       Fwd01Args fa{};
@@ -1009,10 +1008,9 @@ struct trpo_engine {
       fa.H1 = head == RowEpi::kPrepHead ? hout[1] : nullptr;
       fa.H2 = hout[2];
       fa.img = fw_img;
-      fa.am_w0 = wt ? am_wt(0) : am_w(0);
-      fa.am_w1 = wt ? am_wt(1) : am_w(1);
-      std::snprintf(t, sizeof t, "%s_l01", tag);
-      Scope sp(this, t);
+      fa.am_w0 = am_w(ws, 0);
+      fa.am_w1 = am_w(ws, 1);
+      Scope sp(this, tag, "_l01");
       launch_fwd01(fa, num_cus, stream);
       check_launch();
       l_first = 2;
@@ -1020,11 +1018,9 @@ struct trpo_engine {
     for (int l = l_first; l < L; ++l) {
       RowGemmArgs a = row_args(w[l + 1], wp[l + 1]);
       a.nseg = 1;
-      a.seg[0] = GemmSeg{l == 0 ? X : hout[l], wf[l], wp[l], wp[l + 1], wp[l]};
-      seg3(a.seg[0], wf3[l], plane3_f(l), 0, wp[l]);
-      a.seg[0].amaxA = l == 0 ? am_x() : nullptr;   // hidden activations are tanh outputs, |h| <= 1
-      a.seg[0].amaxB = &wf == &WFt ? am_wt(l) : am_w(l);
-      if (l == 0 && planes_l0()) attach_x_planes(a.seg[0], wf3[0], W0b);
+      // hidden activations are tanh outputs, |h| <= 1
+      a.seg[0] = fwd_seg(l, kW, l == 0 ? X : hout[l], l == 0 ? am_x() : nullptr, ws);
+      if (l == 0 && planes_l0()) attach_x_planes(a.seg[0], W0b);
       // head_fwd 1 (default): the prepare and the loss heads (the prepare outputs leave through LDS as coalesced
       // rows: C4 3.6 -> 3.1 ms); 2: the loss heads, and the prepare head for <= 8 actions
       const int hfo = g_options.head_fwd;
@@ -1039,7 +1035,7 @@ struct trpo_engine {
         hf.K = w[l];
         hf.Kpad = wp[l];
         hf.H = l == 0 ? X : hout[l];
-        hf.W = wf[l];
+        hf.W = ws.wf[l];
         hf.bias = th + offb[l];
         hf.old = old;
         hf.act = act;
@@ -1054,9 +1050,7 @@ struct trpo_engine {
           hf.am_d = am_d(L - 1);
           hf.am_ds = am_ds(L - 1);
         }
-        char t[32];
-        std::snprintf(t, sizeof t, "%s_l%d", tag, l);
-        Scope sp(this, t);
+        Scope sp(this, tag, l);
         launch_head_fwd(hf, num_cus, stream);
         check_launch();
         continue;
@@ -1081,9 +1075,7 @@ struct trpo_engine {
           a.ea.amax2 = am_ds(L - 1);
         }
       }
-      char t[32];
-      std::snprintf(t, sizeof t, "%s_l%d", tag, l);
-      Scope sp(this, t);
+      Scope sp(this, tag, l);
       launch_rowgemm(a, stream);
       check_launch();
     }
@@ -1127,7 +1119,7 @@ struct trpo_engine {
     am_reset(am_d(0), L);
     am_reset(am_ds(L - 1), 1);
     if (use_fused16() && g_options.ls_fused == 1) fused16_forward(theta, true);   // fwd_loss16's prepare form
-    else forward(WF, WF3, theta, H, RowEpi::kPrepHead, "fwd");
+    else forward(cur_set(), theta, H, RowEpi::kPrepHead, "fwd");
     // KL_ff plain backward: DH_l = D_l W_l^T ; D_{l-1} = DH (1-H^2) ; E_{l-1} = -2 DH H.
     // D_0 is never written (the R-backward stops at RD_0), E_{L-2} not under the fused tail, which
     // recomputes it from H and D_{L-1}.
@@ -1189,10 +1181,7 @@ struct trpo_engine {
       }
       RowGemmArgs a = row_args(w[l], wp[l]);
       a.nseg = 1;
-      a.seg[0] = GemmSeg{D[l], WB[l], wp[l + 1], wp[l], wp[l + 1]};
-      seg3(a.seg[0], WB3[l], plane3_b(l), 0, wp[l + 1]);
-      a.seg[0].amaxA = am_d(l);
-      a.seg[0].amaxB = am_w(l);
+      a.seg[0] = bwd_seg(l, kW, D[l], am_d(l));
       // both: kPrepBwd ; E only (D_0): kPrepBwdE ; D only: kPgBwd, whose epilogue is DH (1-H^2)
       a.epi = need_d ? (need_e ? RowEpi::kPrepBwd : RowEpi::kPgBwd) : RowEpi::kPrepBwdE;
       a.ea.H = H[l];
@@ -1200,9 +1189,7 @@ struct trpo_engine {
       a.ea.amax0 = need_d ? am_d(l - 1) : nullptr;
       a.ea.out1 = need_d && need_e ? E[l - 1] : nullptr;
       a.ea.ldo = wp[l];
-      char t[32];
-      std::snprintf(t, sizeof t, "bwd_l%d", l);
-      Scope sp(this, t);
+      Scope sp(this, "bwd", l);
       launch_rowgemm(a, stream);
       check_launch();
     }
@@ -1228,6 +1215,7 @@ struct trpo_engine {
     allreduce_f32(out, (size_t)P);
   }
 
+  // layer l's weight-gradient block into the slabs, profiled as "<tag>_l<l>"
   void wgrad_layer(int l, int nseg, WSeg s0, WSeg s1, int colsum_seg, const int* skip, const char* tag) {
     WGradArgs a{};
     a.rows = (int)n;
@@ -1242,9 +1230,19 @@ struct trpo_engine {
     a.dst = slab_dst(l);
     a.skip = skip;
     a.f16 = f16;
-    Scope sp(this, tag);
+    Scope sp(this, tag, l);
     launch_wgrad(a, stream);
     check_launch();
+  }
+  // the FVP's weight gradients of layers [l0, l1): (Hv)_W_l = RH_l^T D_l + H_l^T RD_l ; (Hv)_b_l = colsum RD_l
+  void fvp_wgrads(int l0, int l1, const int* skip) {
+    for (int l = l0; l < l1; ++l) {
+      if (l == 0)
+        wgrad_layer(0, 1, WSeg{X, RD[0], wp[0], wp[1], am_x(), am_rd(0)}, WSeg{}, 0, skip, "fvp_wgrad");
+      else
+        wgrad_layer(l, 2, WSeg{RH[l], D[l], wp[l], wp[l + 1], am_rh(l), am_d(l)},
+                    WSeg{H[l], RD[l], wp[l], wp[l + 1], nullptr, am_rd(l)}, 1, skip, "fvp_wgrad");
+    }
   }
 
   // flatgrad(surr) (trpo_inksci.py:54) -> g (all ranks)
@@ -1280,28 +1278,20 @@ struct trpo_engine {
       }
       RowGemmArgs a = row_args(w[l], wp[l]);
       a.nseg = 1;
-      a.seg[0] = GemmSeg{DS[l], WB[l], wp[l + 1], wp[l], wp[l + 1]};
-      seg3(a.seg[0], WB3[l], plane3_b(l), 0, wp[l + 1]);
-      a.seg[0].amaxA = am_ds(l);
-      a.seg[0].amaxB = am_w(l);
+      a.seg[0] = bwd_seg(l, kW, DS[l], am_ds(l));
       a.epi = RowEpi::kPgBwd;
       a.ea.H = H[l];
       a.ea.out0 = DS[l - 1];
       a.ea.amax0 = am_ds(l - 1);
       a.ea.ldo = wp[l];
-      char t[32];
-      std::snprintf(t, sizeof t, "pg_bwd_l%d", l);
-      Scope sp(this, t);
+      Scope sp(this, "pg_bwd", l);
       launch_rowgemm(a, stream);
       check_launch();
     }
     // with DS_{L-2} from the prepare pass the head layer's weight gradient is already in the slabs
-    for (int l = r0f ? 1 : 0; l < (have_ds ? L - 1 : L); ++l) {
-      char t[32];
-      std::snprintf(t, sizeof t, "pg_wgrad_l%d", l);
+    for (int l = r0f ? 1 : 0; l < (have_ds ? L - 1 : L); ++l)
       wgrad_layer(l, 1, WSeg{act_in(l), DS[l], wp[l], wp[l + 1], l == 0 ? am_x() : nullptr, am_ds(l)}, WSeg{}, 0,
-                  nullptr, t);
-    }
+                  nullptr, "pg_wgrad");
     reduce_grad(g, nullptr);
   }
 
@@ -1333,7 +1323,7 @@ struct trpo_engine {
       check_launch();
     }
     ensure_w3();
-    split_parts(false, true, false, true, WF, WF3, skip, "split_v");
+    split_parts(false, true, false, true, cur_set(), skip, "split_v");
     am_reset(am_rh(0), L);
     am_reset(am_rd(0), L);
     // R-forward (the fused tail takes the last layer's)
@@ -1375,23 +1365,14 @@ struct trpo_engine {
     }
     for (int l = l_first; l < Lf; ++l) {
       RowGemmArgs a = row_args(w[l + 1], wp[l + 1]);
-      float* Vpart = WF[l] + (size_t)wp[l] * wp[l + 1];
       if (l == 0) {
         a.nseg = 1;
-        a.seg[0] = GemmSeg{X, Vpart, wp[0], wp[1], wp[0]};
-        seg3(a.seg[0], WF3[l], plane3_f(l), 1, wp[l]);
-        a.seg[0].amaxA = am_x();
-        a.seg[0].amaxB = am_v(0);
-        if (planes_l0()) attach_x_planes(a.seg[0], WF3[0] + 3 * plane3_f(0), V0b);
+        a.seg[0] = fwd_seg(0, kV, X, am_x(), cur_set());
+        if (planes_l0()) attach_x_planes(a.seg[0], V0b);
       } else {
         a.nseg = 2;
-        a.seg[0] = GemmSeg{RH[l], WF[l], wp[l], wp[l + 1], wp[l]};
-        a.seg[1] = GemmSeg{H[l], Vpart, wp[l], wp[l + 1], wp[l]};
-        seg3(a.seg[0], WF3[l], plane3_f(l), 0, wp[l]);
-        seg3(a.seg[1], WF3[l], plane3_f(l), 1, wp[l]);
-        a.seg[0].amaxA = am_rh(l);
-        a.seg[0].amaxB = am_w(l);
-        a.seg[1].amaxB = am_v(l);
+        a.seg[0] = fwd_seg(l, kW, RH[l], am_rh(l), cur_set());
+        a.seg[1] = fwd_seg(l, kV, H[l], nullptr, cur_set());
       }
       a.skip = skip;
       a.ea.bias = v + offb[l];
@@ -1410,9 +1391,7 @@ struct trpo_engine {
         a.ea.amax0 = am_rd(L - 1);
         a.ea.invN = 1.0 / (double)n_global;
       }
-      char tag[32];
-      std::snprintf(tag, sizeof tag, "fvp_rfwd_l%d", l);
-      Scope sp(this, tag);
+      Scope sp(this, "fvp_rfwd", l);
       launch_rowgemm(a, stream);
       check_launch();
     }
@@ -1452,82 +1431,56 @@ struct trpo_engine {
       ta.invN = 1.0 / (double)n_global;
       ta.dst = slab_dst(l);
       ta.skip = skip;
-      char tag[32];
-      std::snprintf(tag, sizeof tag, "fvp_tail_l%d", l);
-      Scope sp(this, tag);
+      Scope sp(this, "fvp_tail", l);
       launch_tail_pack(tp, stream);
       launch_fvp_tail(ta, stream);
       check_launch();
     }
-    const bool tail_fused = tail;
     // layer 1's R-backward fused with layer 0's weight gradient when layer 1 is not inside the tail
-    const bool r0f = use_rbwd0() && (tail_fused ? L - 2 : L - 1) >= 1;
-    auto r_backward = [&]() {
-      // R-backward: RDH_l = RD_l W_l^T + D_l V_l^T ; RD_{l-1} = RDH (1-H_l^2) + E_{l-1} RH_l
-      for (int l = tail_fused ? L - 2 : L - 1; l >= 1; --l) {
-        if (l == 1 && r0f) {
-          RBwd0Args a = rbwd0_args(skip);
-          a.nseg = 2;
-          a.A0 = RD[1];
-          a.A1 = D[1];
-          if (cache.d1_plane) {
-            a.A1h = D1h;
-            a.a1_mpad = cache.d1_mpad;
-            a.eA1p = pl_e + 1;
-            if (cache.d1_tiled) a.eA1t = eD1t;
-          }
-          a.am_a0 = am_rd(1);
-          a.am_a1 = am_d(1);
-          a.E = E[0];
-          a.RH = RH[1];
-          Scope sp(this, "fvp_rbwdwg_l1");
-          launch_rbwd0(a, stream);
-          check_launch();
-          continue;
-        }
-        RowGemmArgs a = row_args(w[l], wp[l]);
+    const bool r0f = use_rbwd0() && Lf - 1 >= 1;
+    // R-backward: RDH_l = RD_l W_l^T + D_l V_l^T ; RD_{l-1} = RDH (1-H_l^2) + E_{l-1} RH_l
+    for (int l = Lf - 1; l >= 1; --l) {
+      if (l == 1 && r0f) {
+        RBwd0Args a = rbwd0_args(skip);
         a.nseg = 2;
-        a.seg[0] = GemmSeg{RD[l], WB[l], wp[l + 1], wp[l], wp[l + 1]};
-        a.seg[1] = GemmSeg{D[l], WB[l] + (size_t)wp[l + 1] * wp[l], wp[l + 1], wp[l], wp[l + 1]};
-        seg3(a.seg[0], WB3[l], plane3_b(l), 0, wp[l + 1]);
-        seg3(a.seg[1], WB3[l], plane3_b(l), 1, wp[l + 1]);
-        a.seg[0].amaxA = am_rd(l);
-        a.seg[0].amaxB = am_w(l);
-        a.seg[1].amaxA = am_d(l);
-        a.seg[1].amaxB = am_v(l);
-        a.skip = skip;
-        a.epi = RowEpi::kRBwd;
-        a.ea.H = H[l];
-        a.ea.E = E[l - 1];
-        a.ea.RH = RH[l];
-        a.ea.out0 = RD[l - 1];
-        a.ea.amax0 = am_rd(l - 1);
-        a.ea.ldo = wp[l];
-        char tag[32];
-        std::snprintf(tag, sizeof tag, "fvp_rbwd_l%d", l);
-        Scope sp(this, tag);
-        launch_rowgemm(a, stream);
+        a.A0 = RD[1];
+        a.A1 = D[1];
+        if (cache.d1_plane) {
+          a.A1h = D1h;
+          a.a1_mpad = cache.d1_mpad;
+          a.eA1p = pl_e + 1;
+          if (cache.d1_tiled) a.eA1t = eD1t;
+        }
+        a.am_a0 = am_rd(1);
+        a.am_a1 = am_d(1);
+        a.E = E[0];
+        a.RH = RH[1];
+        Scope sp(this, "fvp_rbwdwg_l1");
+        launch_rbwd0(a, stream);
         check_launch();
+        continue;
       }
-    };
-    auto weight_grads = [&]() {
-      // weight gradients: (Hv)_W_l = RH_l^T D_l + H_l^T RD_l ; (Hv)_b_l = colsum RD_l
-      for (int l = r0f ? 1 : 0; l < (tail_fused ? L - 1 : L); ++l) {
-        char tag[32];
-        std::snprintf(tag, sizeof tag, "fvp_wgrad_l%d", l);
-        if (l == 0)
-          wgrad_layer(0, 1, WSeg{X, RD[0], wp[0], wp[1], am_x(), am_rd(0)}, WSeg{}, 0, skip, tag);
-        else
-          wgrad_layer(l, 2, WSeg{RH[l], D[l], wp[l], wp[l + 1], am_rh(l), am_d(l)},
-                      WSeg{H[l], RD[l], wp[l], wp[l + 1], nullptr, am_rd(l)}, 1, skip, tag);
-      }
-    };
-    r_backward();
-    weight_grads();
+      RowGemmArgs a = row_args(w[l], wp[l]);
+      a.nseg = 2;
+      a.seg[0] = bwd_seg(l, kW, RD[l], am_rd(l));
+      a.seg[1] = bwd_seg(l, kV, D[l], am_d(l));
+      a.skip = skip;
+      a.epi = RowEpi::kRBwd;
+      a.ea.H = H[l];
+      a.ea.E = E[l - 1];
+      a.ea.RH = RH[l];
+      a.ea.out0 = RD[l - 1];
+      a.ea.amax0 = am_rd(l - 1);
+      a.ea.ldo = wp[l];
+      Scope sp(this, "fvp_rbwd", l);
+      launch_rowgemm(a, stream);
+      check_launch();
+    }
+    fvp_wgrads(r0f ? 1 : 0, Lf, skip);
     reduce_grad(out, skip);
   }
 
-  ChainArgs chain_args(const float* v, const int* skip) const {
+  ChainArgs chain_args(const ImageSet& is, const float* v, const int* skip) const {
     ChainArgs ca{};
     ca.n = (int)n;
     ca.L = L;
@@ -1546,31 +1499,35 @@ struct trpo_engine {
     }
     ca.P = Pm;
     ca.v = v;
-    ca.img = chain_img;
-    ca.tab = chain_tab;
-    ca.nchunks = chain_nchunks;
+    ca.img = is.img;
+    ca.tab = is.tab;
+    ca.nchunks = is.nchunks;
     ca.invN = 1.0 / (double)n_global;
     ca.skip = skip;
     return ca;
   }
+  // the chain images of theta (when stale) and of the tangent v
+  void chain_w_images(const float* v) {
+    if (cache.chain_w_valid) return;
+    Scope sp(this, "fvp_img_w");
+    launch_chain_img(chain_set.jobs, theta, v, 0, nullptr, stream);
+    check_launch();
+    cache.chain_w_valid = true;
+  }
+  void chain_images(const float* v, const int* skip) {
+    chain_w_images(v);
+    Scope sp(this, "fvp_img_v");
+    launch_chain_img(chain_set.jobs, theta, v, 1, skip, stream);
+    check_launch();
+  }
 
   // the whole Hv in one launch (fused.hip) + the slab reduction
   void fvp_fused(const float* v, float* out, const int* skip) {
-    if (!cache.chain_w_valid) {
-      Scope sp(this, "fvp_img_w");
-      launch_chain_img(chain_jobs, theta, v, 0, nullptr, stream);
-      check_launch();
-      cache.chain_w_valid = true;
-    }
-    {
-      Scope sp(this, "fvp_img_v");
-      launch_chain_img(chain_jobs, theta, v, 1, skip, stream);
-      check_launch();
-    }
+    chain_images(v, skip);
     const int variant = g_options.fused == 1 ? 1 : 2;   // 3 (f16) where fused16.hip does not apply: 4 waves
     const int rb = fused_fvp_states_per_group(variant);
     FusedArgs fa{};
-    fa.c = chain_args(v, skip);
+    fa.c = chain_args(chain_set, v, skip);
     fa.slab = slab;
     fa.slab_stride = slab_stride;
     for (int l = 0; l < L; ++l) fa.offW[l] = offW[l];
@@ -1584,12 +1541,7 @@ struct trpo_engine {
       launch_fvp_fused(fa, grid, variant, stream);
       check_launch();
     }
-    {
-      Scope sp(this, "reduce");
-      launch_reduce_slab(slab, grid, slab_stride, P, out, skip, stream);
-      check_launch();
-    }
-    allreduce_f32(out, (size_t)P);
+    reduce_grad(out, skip, grid);
   }
 
   // fused16.hip's arguments for the tangent v (the FVP) or none (the policy gradient), and its grid: persistent
@@ -1597,15 +1549,12 @@ struct trpo_engine {
   Fused16Args fused16_args(const float* v, const int* skip, int& grid) {
     const int rb = fused16_states_per_group();
     Fused16Args fa{};
-    fa.f.c = chain_args(v, skip);
-    fa.f.c.img = f16_img;
-    fa.f.c.tab = f16_tab;
-    fa.f.c.nchunks = f16_nchunks;
+    fa.f.c = chain_args(f16_set, v, skip);
     fa.f.slab = slab;
     fa.f.slab_stride = slab_stride;
     for (int l = 0; l < L; ++l) fa.f.offW[l] = offW[l];
     fa.f.ngroups = (int)((n + rb - 1) / rb);
-    fa.img_e = f16_e;
+    fa.img_e = f16_set.e;
     fa.am_x = am_x();
     fa.am_d1 = am_d(1);
     fa.am_d2 = L == 3 ? am_d(2) : nullptr;
@@ -1620,7 +1569,7 @@ struct trpo_engine {
   void fused16_w_images() {
     if (cache.f16_w_valid) return;
     Scope sp(this, "fvp_img_w");
-    launch_fused16_img(f16_jobs, theta, nullptr, 0, nullptr, f16_e, stream);
+    launch_fused16_img(f16_set.jobs, theta, nullptr, 0, nullptr, f16_set.e, stream);
     check_launch();
     cache.f16_w_valid = true;
   }
@@ -1630,7 +1579,7 @@ struct trpo_engine {
     fused16_w_images();
     if (!f16_v_img_ready) {   // else the previous CG step's launch built v's images (cg())
       Scope sp(this, "fvp_img_v");
-      launch_fused16_img(f16_jobs, theta, v, 1, skip, f16_e, stream);
+      launch_fused16_img(f16_set.jobs, theta, v, 1, skip, f16_set.e, stream);
       check_launch();
     }
     f16_v_img_ready = false;
@@ -1645,12 +1594,7 @@ struct trpo_engine {
       *defer = grid;
       return;
     }
-    {
-      Scope sp(this, "reduce");
-      launch_reduce_slab(slab, grid, slab_stride, P, out, skip, stream);
-      check_launch();
-    }
-    allreduce_f32(out, (size_t)P);
+    reduce_grad(out, skip, grid);
   }
 
   // g's slabs in one launch on the same machinery (fused16.hip, PG form): the surr backward from DS_2 and every
@@ -1669,18 +1613,8 @@ struct trpo_engine {
 
   // the same Hv with the row-local part (R-forward, R-head, R-backward) in one fused launch
   void fvp_chain(const float* v, float* out, const int* skip) {
-    if (!cache.chain_w_valid) {
-      Scope sp(this, "fvp_img_w");
-      launch_chain_img(chain_jobs, theta, v, 0, nullptr, stream);
-      check_launch();
-      cache.chain_w_valid = true;
-    }
-    {
-      Scope sp(this, "fvp_img_v");
-      launch_chain_img(chain_jobs, theta, v, 1, skip, stream);
-      check_launch();
-    }
-    const ChainArgs ca = chain_args(v, skip);
+    chain_images(v, skip);
+    const ChainArgs ca = chain_args(chain_set, v, skip);
     {
       Scope sp(this, "fvp_chain");
       launch_fvp_chain(ca, chain_otm, stream);
@@ -1698,16 +1632,7 @@ struct trpo_engine {
       }
       check_launch();
     }
-    // weight gradients: (Hv)_W_l = RH_l^T D_l + H_l^T RD_l ; (Hv)_b_l = colsum RD_l
-    for (int l = 0; l < L; ++l) {
-      char tag[32];
-      std::snprintf(tag, sizeof tag, "fvp_wgrad_l%d", l);
-      if (l == 0)
-        wgrad_layer(0, 1, WSeg{X, RD[0], wp[0], wp[1], am_x(), am_rd(0)}, WSeg{}, 0, skip, tag);
-      else
-        wgrad_layer(l, 2, WSeg{RH[l], D[l], wp[l], wp[l + 1], am_rh(l), am_d(l)},
-                    WSeg{H[l], RD[l], wp[l], wp[l + 1], nullptr, am_rd(l)}, 1, skip, tag);
-    }
+    fvp_wgrads(0, L, skip);
     reduce_grad(out, skip);
   }
 
@@ -1729,12 +1654,12 @@ struct trpo_engine {
         // iteration's V image, which that FVP then does not launch (fvp_fused16)
         const CgStepArgs ca{slab, slabs, it, slab_stride, P, hv, xo, r, pc, z, sc, partA, fl, cg_ticket};
         const bool img = use_fused16() && it + 1 < iters;
-        launch_cg_step_slabs(ca, img ? &f16_jobs : nullptr, f16_e, stream);
+        launch_cg_step_slabs(ca, img ? &f16_set.jobs : nullptr, f16_set.e, stream);
         f16_v_img_ready = img;
       } else if (slabs > 0 && g_options.cg_p_img != 0 && use_fused16() && it + 1 < iters) {
         // the p update and the next FVP's V images in one launch (the next p in the other buffer)
         launch_cg_iter_slabs(slab, slabs, slab_stride, hv, xo, r, pc, z, P, sc, partA, partB, fl, it, stream, false);
-        launch_cg_p_img16(f16_jobs, r, pc, pn, P, sc, partB, fl, it, f16_e, stream);
+        launch_cg_p_img16(f16_set.jobs, r, pc, pn, P, sc, partB, fl, it, f16_set.e, stream);
         f16_v_img_ready = true;
         std::swap(pc, pn);
       } else if (slabs > 0) {
@@ -1760,7 +1685,7 @@ struct trpo_engine {
   void fused16_forward(const float* th, bool prep) {
     {
       Scope sp(this, prep ? "fwd_img" : "ls_img");
-      launch_fused16_img(f16_ljobs, th, nullptr, 0, nullptr, f16_le, stream);
+      launch_fused16_img(f16_loss_set.jobs, th, nullptr, 0, nullptr, f16_loss_set.e, stream);
       check_launch();
     }
     FwdLoss16Args la{};
@@ -1773,10 +1698,10 @@ struct trpo_engine {
     la.X = X;
     la.theta = th;
     for (int l = 0; l < L; ++l) la.offb[l] = offb[l];
-    la.img = f16_limg;
-    la.tab = f16_ltab;
-    la.nchunks = f16_lnchunks;
-    la.img_e = f16_le;
+    la.img = f16_loss_set.img;
+    la.tab = f16_loss_set.tab;
+    la.nchunks = f16_loss_set.nchunks;
+    la.img_e = f16_loss_set.e;
     la.am_x = am_x();
     la.old = old;
     la.act = act;
@@ -1806,8 +1731,8 @@ struct trpo_engine {
     }
     PackArgs pa = pack_args(WFt, nullptr, 2);
     launch_pack(pa, th, 0, nullptr, stream);
-    split_parts(true, false, false, false, WFt, WFt3, nullptr, "split_t");
-    forward(WFt, WFt3, th, RH, RowEpi::kLossHead, "ls_fwd");
+    split_parts(true, false, false, false, trial_set(), nullptr, "split_t");
+    forward(trial_set(), th, RH, RowEpi::kLossHead, "ls_fwd");
     reduce_losses(1, nullptr);
   }
 
@@ -1818,25 +1743,33 @@ struct trpo_engine {
           "tail values are set but the advantage estimator is TRPO_ADV_RETURNS: select TRPO_ADV_GAE or clear them");
   }
 
+  // Two-pass moments of c = y - sub (sub may be NULL) over all ranks: c to centered_out (may alias y), its sum to
+  // *mean_slot, then the sum of (c - mean)^2 to *sumsq_slot, mean = *mean_slot * inv_n.  `part` holds kRedBlocks
+  // partials; without an engine (one process) nothing is all-reduced.
+  static void moments(trpo_engine* e, hipStream_t s, double* part, const double* y, const double* sub,
+                      double* centered_out, int64_t count, double inv_n, double* mean_slot, double* sumsq_slot) {
+    launch_adv_center_partials(y, sub, centered_out, count, part, s);
+    launch_sum_finish(part, mean_slot, s);
+    if (e) e->allreduce_f64(mean_slot, 1);
+    launch_adv_sq_partials(centered_out, count, mean_slot, inv_n, part, s);
+    launch_sum_finish(part, sumsq_slot, s);
+    if (e) e->allreduce_f64(sumsq_slot, 1);
+  }
+
   void compute_advantages(double gamma) {
     REQUIRE(have_rewards, "no rewards: call trpo_set_rewards first");
     check_estimator_state();
+    const double inv_n = 1.0 / (double)n_global;
     if (adv_kind == TRPO_ADV_GAE) {
       // one scan writes the returns and the raw advantages; the standardisation then runs in place, the
       // launches of standardize()
       launch_gae(rewards, have_baseline ? baseline : nullptr, starts, have_tail ? tail : nullptr, n, gamma,
                  adv_lambda, adv64, returns, scan_ws, stream);
-      launch_adv_center_partials(adv64, nullptr, adv64, n, partA, stream);
+      moments(this, stream, partA, adv64, nullptr, adv64, n, inv_n, dscal, dscal + 1);
     } else {
       launch_discount(rewards, starts, n, gamma, returns, scan_ws, stream);
-      launch_adv_center_partials(returns, have_baseline ? baseline : nullptr, adv64, n, partA, stream);
+      moments(this, stream, partA, returns, have_baseline ? baseline : nullptr, adv64, n, inv_n, dscal, dscal + 1);
     }
-    launch_sum_finish(partA, dscal, stream);
-    allreduce_f64(dscal, 1);
-    const double inv_n = 1.0 / (double)n_global;
-    launch_adv_sq_partials(adv64, n, dscal, inv_n, partA, stream);
-    launch_sum_finish(partA, dscal + 1, stream);
-    allreduce_f64(dscal + 1, 1);
     launch_adv_normalize(adv64, adv32, n, dscal, dscal + 1, inv_n, stream);
     check_launch();
     cache.advantages_computed();
@@ -1846,12 +1779,7 @@ struct trpo_engine {
   // engine's stream; the same kernels and sums as compute_advantages
   void standardize(double* adv, float* adv32, int64_t cnt, int64_t cnt_global) {
     const double inv_n = 1.0 / (double)cnt_global;
-    launch_adv_center_partials(adv, nullptr, adv, cnt, partA, stream);
-    launch_sum_finish(partA, dscal + 6, stream);
-    allreduce_f64(dscal + 6, 1);
-    launch_adv_sq_partials(adv, cnt, dscal + 6, inv_n, partA, stream);
-    launch_sum_finish(partA, dscal + 7, stream);
-    allreduce_f64(dscal + 7, 1);
+    moments(this, stream, partA, adv, nullptr, adv, cnt, inv_n, dscal + 6, dscal + 7);
     launch_adv_normalize(adv, adv32, cnt, dscal + 6, dscal + 7, inv_n, stream);
     check_launch();
   }
@@ -1861,17 +1789,9 @@ struct trpo_engine {
     REQUIRE(cache.have_returns, "no returns: compute the advantages first");
     if (!ev_tmp) ev_tmp = dalloc<double>(cap);
     const double inv_n = 1.0 / (double)n_global;
-    auto var = [&](const double* ypred, int slot) {
-      launch_adv_center_partials(returns, ypred, ev_tmp, n, partA, stream);
-      launch_sum_finish(partA, dscal + slot, stream);
-      allreduce_f64(dscal + slot, 1);
-      launch_adv_sq_partials(ev_tmp, n, dscal + slot, inv_n, partA, stream);
-      launch_sum_finish(partA, dscal + slot + 1, stream);
-      allreduce_f64(dscal + slot + 1, 1);
-      check_launch();
-    };
-    var(nullptr, 2);
-    var(have_baseline ? baseline : nullptr, 4);
+    moments(this, stream, partA, returns, nullptr, ev_tmp, n, inv_n, dscal + 2, dscal + 3);
+    moments(this, stream, partA, returns, have_baseline ? baseline : nullptr, ev_tmp, n, inv_n, dscal + 4, dscal + 5);
+    check_launch();
     double h[6];
     copy_out(h, dscal, sizeof h, TRPO_MEM_HOST);
     const double vary = h[3] * inv_n, vard = h[5] * inv_n;
@@ -2350,10 +2270,7 @@ int trpo_standardize(trpo_engine* e, double* adv, int64_t n, int64_t n_global, f
       double* part = st.tmp<double>(kRedBlocks);
       double* sums = st.tmp<double>(2);
       const double inv_n = 1.0 / (double)n;
-      launch_adv_center_partials(da, nullptr, da, n, part, s);
-      launch_sum_finish(part, sums, s);
-      launch_adv_sq_partials(da, n, sums, inv_n, part, s);
-      launch_sum_finish(part, sums + 1, s);
+      trpo_engine::moments(nullptr, s, part, da, nullptr, da, n, inv_n, sums, sums + 1);
       launch_adv_normalize(da, d32, n, sums, sums + 1, inv_n, s);
       check_launch();
     }

@@ -12,8 +12,9 @@ namespace trpo {
 
 // Kernel-variant switches (defaults from TRPO_SPLIT_MFMA, TRPO_SPLIT_WG, TRPO_CHAIN, TRPO_SPLIT_F16,
 // TRPO_SPLIT_MIN_K, TRPO_GRAPHS, TRPO_TAIL, TRPO_FUSED, TRPO_LOW_SEG, TRPO_PLANES, TRPO_RBWD0, TRPO_HBWD2,
-// TRPO_HEAD_FWD, TRPO_SPLITS, TRPO_PG_SPLITS in gemm.hip; runtime-settable through trpo_set_option for A/B
-// and parity tests).
+// TRPO_HEAD_FWD, TRPO_SPLITS, TRPO_PG_SPLITS, TRPO_LS_FUSED, TRPO_CG_FUSE_REDUCE, TRPO_CG_P_IMG, TRPO_RFWD01,
+// TRPO_FWD01 in gemm.hip, in the order of the fields; runtime-settable through trpo_set_option for A/B and
+// parity tests).
 struct Options {
   int split_mfma;  // row GEMMs with N > 128 on the split MFMA: 0 off (f32 MFMA), 5 = 256 x 256 tile at
                    // BK 32 on f16 planes (default), 6 = 256 x 256 at BK 16, any other value = 128 x 256

@@ -147,10 +147,9 @@ struct trpo_vf {
     if (have_feat && rows != n) have_tgt = false;
     n = rows;
     n_global = rows_global;
-    int64_t rps = (n + S - 1) / S;
-    rps = std::max<int64_t>(64, (rps + 31) / 32 * 32);
-    rows_per_split = (int)rps;
-    active_splits = (int)std::max<int64_t>(1, (n + rps - 1) / rps);
+    const SplitGeom sg = split_geometry(n, S);
+    rows_per_split = sg.rows_per_split;
+    active_splits = sg.active;
   }
 
   void pack() {
