@@ -263,12 +263,20 @@ int trpo_gae(const double* rewards, const double* values, const uint8_t* episode
  * with obs <= 128 run the fused tail: 1 = on, the default; 0 = the plane and row GEMM launches).
  * "fwd01" (the prepare and line-search forwards through layers 0 and 1 as one launch, rfwd.hip, at the same
  * shapes: 1 = on, the default; 0 = the plane and row GEMM launches).
+ * "rh1_planes" (where "rfwd01" and "rbwd0" both run on the f16 split: rfwd01 writes RH_1 as two row-paired f16
+ * planes, hi and lo, in the bytes of the f32 matrix, and its readers, rbwd0's epilogue and the layer-1 weight
+ * gradient, fetch the hi plane alone where their "low_seg" test fires and both planes where it does not:
+ * 1 = on, the default; 0 = RH_1 in f32, every launch and every bit as without the option).
  * "ls_fused" = 2 mixes two forwards inside one line search (loss_before from the per-layer forward, the
  * trials' losses from fwd_loss16); it exists for A/B timing and is held to the same parity tests.
  * Rejected variants (other tiles, last-layer fusions, 16-bit E planes, a second stream) were removed
  * from the build in round 4; tools/patches/pruned_variants.patch restores them.
  * Process-wide. */
 int trpo_set_option(const char* name, int value);
+/* Host-only: whether a batch whose X planes have x_mpad rows (n rounded up to 256) is within the row limit of the
+ * one-launch forwards ("rfwd01" / "fwd01") and of the row-paired planes ("rh1_planes").  The engine's gates and the
+ * launchers read the same two predicates, so a default-on path cannot throw on a row count the fallback takes. */
+int trpo_plane_rows_ok(int64_t x_mpad, int* rfwd01_ok, int* pair_planes_ok);
 int trpo_get_option(const char* name, int* value);
 
 /* ---- profiling: per-launch HIP events on the engine stream ------------------------- */

@@ -25,8 +25,9 @@ import sys
 SPECS = {
     "fvp_rfwd_l0": ("rowgemm_pl_kernel<1, 1>", 1, 0),                       # X planes, kRHidden (plane.hip)
     "fvp_rfwd_l1": ("rowgemm3_kernel<4, 2, 2, 4, 11, 2, 1, 2, 32>", 1, 0),  # kRZ into the tail (BK 32)
-    "fvp_rfwd01": ("rfwd01_kernel<8>", 1, 0),                               # layers 0 + 1 R-forward (rfwd.hip)
-    "fvp_rbwdwg_l1": ("rbwd0_kernel<2>", 1, 0),                             # R-backward + X^T RD_0 (rbwd0.hip)
+    # (second template argument: RH1 as f32, false, or as planes, true: one of the two runs per FVP)
+    "fvp_rfwd01": ("rfwd01_kernel<8, ", 1, 0),                              # layers 0 + 1 R-forward (rfwd.hip)
+    "fvp_rbwdwg_l1": ("rbwd0_kernel<2, ", 1, 0),                            # R-backward + X^T RD_0 (rbwd0.hip)
     "fvp_tail_l2": ("fvp_tail_kernel", 1, 0),
     # C2 / C3: the one-launch FVP (fused16.hip <FW, LB, TI0, OTA, MODE, NH> with MODE 0, the only zero argument;
     # every substring must be in the name)
@@ -34,7 +35,8 @@ SPECS = {
 }
 # tags whose kernel is shared with a 1-segment policy-gradient launch: keep the long ones
 LONGEST = {
-    "fvp_wgrad_l1": "wgrad3_kernel<4, 2, 2, 4, 2, 1, 2>",
+    # (f32 RH1: <..., 1, 2, false>; RH1 planes: <..., 2, 2, true>)
+    "fvp_wgrad_l1": "wgrad3_kernel<4, 2, 2, 4, 2, ",
 }
 
 

@@ -104,6 +104,7 @@ SIGNATURES = {
     "trpo_gae": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p,
                          c_int]),
     "trpo_set_option": (c_int, [c_char_p, c_int]),
+    "trpo_plane_rows_ok": (c_int, [c_int64, POINTER(c_int), POINTER(c_int)]),
     "trpo_get_option": (c_int, [c_char_p, POINTER(c_int)]),
     "trpo_profile_enable": (c_int, [c_void_p, c_int]),
     "trpo_profile_query": (c_int, [c_void_p, c_char_p, c_int]),

@@ -166,7 +166,7 @@ struct trpo_engine {
   // running max whenever X changes (layout stride x_mpad = round256(n)), and blocked copies of layer 0's
   // W / V weight planes, re-blocked from WF3 / WFt3 before each use
   uint16_t *Xh = nullptr, *Xl = nullptr, *W0b = nullptr, *V0b = nullptr;
-  int* pl_e = nullptr;   // scale exponents published by the plane producers: [0] = X, [1] = D_1
+  int* pl_e = nullptr;   // scale exponents published by the plane producers: [0] = X, [1] = D_1, [2] = RH_1
   // D_1's f16 hi plane (k-blocked like Xh, stride cache.d1_mpad), written by prepare() for the fused
   // R-backward's one-product D_1 V_1^T segment (rbwd0.hip), and its per-tile scale exponents
   uint16_t* D1h = nullptr;
@@ -253,6 +253,17 @@ struct trpo_engine {
   }
   bool use_rbwd0() const {
     return g_options.rbwd0 != 0 && f16 && x_planes_on() && rbwd0_geom() && rowgemm_uses_split(wp[1], RowEpi::kRBwd);
+  }
+  // RH1 as row-paired f16 planes in RH[1]'s bytes (option rh1_planes): rfwd01 writes them, and its two readers, the
+  // fused R-backward's epilogue and the layer-1 weight gradient on the split kernel, both take planes; decided
+  // per fvp() call, which holds the producer and both readers, so no state outlives the call
+  bool use_rh1_planes() const {
+    return g_options.rh1_planes != 0 && use_rfwd01() && use_rbwd0() && g_options.split_wg != 0 &&
+           wp[1] == kPairLd && pair_planes_rows_ok(x_mpad);
+  }
+  PairPlane rh1_planes() const {
+    const unsigned* hi = reinterpret_cast<const unsigned*>(RH[1]);
+    return PairPlane{hi, hi + pair_plane_dwords(n), pl_e + 2};
   }
   RBwd0Args rbwd0_args(const int* skip) const {
     RBwd0Args a{};
@@ -445,7 +456,8 @@ struct trpo_engine {
     E.assign(L, nullptr);
     for (int l = 1; l < L; ++l) {
       H[l] = dalloc<float>((size_t)cap * wp[l]);
-      RH[l] = dalloc<float>((size_t)cap * wp[l]);
+      // (an even row count: RH[1] also holds RH1's row-paired planes, two planes of ceil(n / 2) row pairs)
+      RH[l] = dalloc<float>((size_t)(cap + (cap & 1)) * wp[l]);
     }
     for (int l = 0; l < L; ++l) {
       D[l] = dalloc<float>((size_t)cap * wp[l + 1]);
@@ -1235,13 +1247,16 @@ struct trpo_engine {
     check_launch();
   }
   // the FVP's weight gradients of layers [l0, l1): (Hv)_W_l = RH_l^T D_l + H_l^T RD_l ; (Hv)_b_l = colsum RD_l
-  void fvp_wgrads(int l0, int l1, const int* skip) {
+  // (rh1p: this FVP's rfwd01 left RH1 as planes)
+  void fvp_wgrads(int l0, int l1, const int* skip, bool rh1p = false) {
     for (int l = l0; l < l1; ++l) {
-      if (l == 0)
+      if (l == 0) {
         wgrad_layer(0, 1, WSeg{X, RD[0], wp[0], wp[1], am_x(), am_rd(0)}, WSeg{}, 0, skip, "fvp_wgrad");
-      else
-        wgrad_layer(l, 2, WSeg{RH[l], D[l], wp[l], wp[l + 1], am_rh(l), am_d(l)},
-                    WSeg{H[l], RD[l], wp[l], wp[l + 1], nullptr, am_rd(l)}, 1, skip, "fvp_wgrad");
+      } else {
+        WSeg s0{RH[l], D[l], wp[l], wp[l + 1], am_rh(l), am_d(l)};
+        if (l == 1 && rh1p) s0.Ap = rh1_planes();
+        wgrad_layer(l, 2, s0, WSeg{H[l], RD[l], wp[l], wp[l + 1], nullptr, am_rd(l)}, 1, skip, "fvp_wgrad");
+      }
     }
   }
 
@@ -1330,6 +1345,7 @@ struct trpo_engine {
     const bool tail = use_tail();
     const int Lf = tail ? L - 1 : L;
     int l_first = 0;
+    const bool rh1p = use_rh1_planes();
     if (use_rfwd01()) {   // layers 0 and 1 in one launch (rfwd.hip): RH1 and the tail's RZ2
       {
         Scope sp(this, "fvp_rfwd_img");
@@ -1357,6 +1373,7 @@ struct trpo_engine {
       ra.am_v1 = am_v(1);
       ra.am_rh1 = am_rh(1);
       ra.am_rz2 = am_rh(2);
+      if (rh1p) ra.e_rh1 = pl_e + 2;
       ra.skip = skip;
       Scope sp(this, "fvp_rfwd01");
       launch_rfwd01(ra, num_cus, stream);
@@ -1455,6 +1472,7 @@ struct trpo_engine {
         a.am_a1 = am_d(1);
         a.E = E[0];
         a.RH = RH[1];
+        if (rh1p) a.RHp = rh1_planes();
         Scope sp(this, "fvp_rbwdwg_l1");
         launch_rbwd0(a, stream);
         check_launch();
@@ -1476,7 +1494,7 @@ struct trpo_engine {
       launch_rowgemm(a, stream);
       check_launch();
     }
-    fvp_wgrads(r0f ? 1 : 0, Lf, skip);
+    fvp_wgrads(r0f ? 1 : 0, Lf, skip, rh1p);
     reduce_grad(out, skip);
   }
 

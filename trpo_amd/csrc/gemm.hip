@@ -41,7 +41,8 @@ Options g_options = {env_int("TRPO_SPLIT_MFMA", 5), env_int("TRPO_SPLIT_WG", 1),
                      env_int("TRPO_HEAD_FWD", 1), env_int("TRPO_SPLITS", 0),
                      env_int("TRPO_PG_SPLITS", 0), env_int("TRPO_LS_FUSED", 1),
                      env_int("TRPO_CG_FUSE_REDUCE", 1), env_int("TRPO_CG_P_IMG", 1),
-                     env_int("TRPO_RFWD01", 1), env_int("TRPO_FWD01", 1)};
+                     env_int("TRPO_RFWD01", 1), env_int("TRPO_FWD01", 1),
+                     env_int("TRPO_RH1_PLANES", 1)};
 
 namespace {
 
@@ -481,10 +482,17 @@ rowgemm3_kernel(const RowGemmArgs args) {
 // operands are row-major activations, so staging transposes: a thread owns one
 // column and 8 consecutive rows (8 coalesced dword loads), splits them and
 // writes one 16-B k-chunk per plane of the [column][16 rows] LDS image.
+// A segment whose A operand comes as row-paired f16 planes (WSeg::Ap, kernels.h PairPlane: a dword = two
+// consecutive rows of one column) needs neither the f32 loads nor the split: the thread's 8 rows of its column
+// are 4 dwords per plane, already in the k order of the chunk, stored to the image as loaded; on the one-product
+// path the lo plane is neither fetched nor written.  The segment's A scale is then the planes' exponent; the
+// low_seg test reads the running-max slots either way.
 // ---------------------------------------------------------------------------
-template <int WM, int WN, int TM, int TN, int OCC, int PF, int NP>
+// PA: segment 0's A operand comes as planes (an instantiation of its own: the f32 form's code is untouched by it)
+template <int WM, int WN, int TM, int TN, int OCC, int PF, int NP, bool PA = false>
 __global__ void __launch_bounds__(WM* WN * 64, OCC)
 wgrad3_kernel(const WGradArgs args) {
+  static_assert(!PA || NP == 2, "plane operands are f16");
   constexpr int BK = 16;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
   constexpr int APL = BM * BK, BPL = BN * BK;
@@ -520,6 +528,8 @@ wgrad3_kernel(const WGradArgs args) {
       one0 = -d >= args.low_seg + pen1;
       one1 = d >= args.low_seg + pen0;
     }
+    // a plane operand's scale is its planes' (after the test, which stays on the running-max slots)
+    if constexpr (PA) eA[0] = __builtin_amdgcn_readfirstlane(*args.seg[0].Ap.e);
   }
 
   f32x16 acc[TM][TN];
@@ -571,14 +581,42 @@ wgrad3_kernel(const WGradArgs args) {
     st.sg = sg;
     // descriptors from the (wave-uniform) segment's pointers, built here: a select between two
     // prebuilt descriptors came out in VGPRs and put every load in a readfirstlane loop
-    const __amdgpu_buffer_rsrc_t ra = desc(sg ? args.seg[1].A : args.seg[0].A, args.seg[0].lda);
     const __amdgpu_buffer_rsrc_t rb = desc(sg ? args.seg[1].B : args.seg[0].B, args.seg[0].ldb);
     const int sa = kt * BK * lda4, sb = kt * BK * ldb4;
-    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PA) {
+      // One load pattern for both kinds of tile, chosen by scalar selects (a branch around the loads kept hipcc
+      // from batching them): 8 A loads per item, for an f32 tile the 8 rows, for a plane tile (sg == 0) the 4 row
+      // pairs of the hi plane, then of the lo plane.  The planes' descriptors cover row pairs [r0 / 2, (r1 + 1) / 2)
+      // (r0 is even: rows_per_split % 16 == 0); lda = kPairLd, so the lane's plane offset is its f32 one with the
+      // 8-row group stride halved.  On the one-product path the lo loads address past the descriptor: they read
+      // 0 and fetch nothing.
+      const bool p0 = sg == 0;
+      const size_t pair0 = (size_t)(r0 >> 1) * kPairLd;
+      const float* const fa = args.seg[1].A + (size_t)r0 * args.seg[0].lda;
+      const void* const b03 = p0 ? (const void*)(args.seg[0].Ap.hi + pair0) : (const void*)fa;
+      const void* const b47 = p0 ? (const void*)(args.seg[0].Ap.lo + pair0) : (const void*)fa;
+      const int bytes = p0 ? (r1 - r0 + 1) / 2 * kPairLd * 4 : (r1 - r0) * lda4;
+      const __amdgpu_buffer_rsrc_t r03 = __builtin_amdgcn_make_buffer_rsrc((void*)b03, 0, bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t r47 = __builtin_amdgcn_make_buffer_rsrc((void*)b47, 0, bytes, 0x00020000);
+      const int s0 = p0 ? sa / 2 : sa, sq = p0 ? kPairLd * 4 : lda4, s4 = p0 ? s0 : sa + 4 * lda4;
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int i = 0; i < AP; ++i)
+      for (int i = 0; i < AP; ++i) {
+        const int v03 = p0 ? vA[i] - ((vA[i] >> 1) & (4 * kPairLd * 4)) : vA[i];
+        const int v47 = (p0 && one0) ? kOob : v03;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) st.va[i][q] = ldbuf(ra, vA[i], sa + q * lda4);
+        for (int q = 0; q < 4; ++q) st.va[i][q] = ldbuf(r03, v03, s0 + q * sq);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) st.va[i][4 + q] = ldbuf(r47, v47, s4 + q * sq);
+      }
+    } else {
+      const __amdgpu_buffer_rsrc_t ra = desc(sg ? args.seg[1].A : args.seg[0].A, args.seg[0].lda);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < AP; ++i)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) st.va[i][q] = ldbuf(ra, vA[i], sa + q * lda4);
+    }
 #pragma unroll
     for (int i = 0; i < BP; ++i)
 #pragma unroll
@@ -620,7 +658,19 @@ wgrad3_kernel(const WGradArgs args) {
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
       const int f = tid + i * NT;
-      if (AI % NT == 0 || f < AI) put(As, APL, f % BM, f / BM, st.va[i], eA[st.sg]);
+      if (AI % NT != 0 && f >= AI) continue;
+      if (PA && st.sg == 0) {
+        // the planes' dwords are the chunk's 8 rows in order
+        typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
+        unsigned short* dst = As + swz16(f % BM, f / BM);
+        *reinterpret_cast<u32x4s*>(dst) = u32x4s{__float_as_uint(st.va[i][0]), __float_as_uint(st.va[i][1]),
+                                                 __float_as_uint(st.va[i][2]), __float_as_uint(st.va[i][3])};
+        if (!one0)
+          *reinterpret_cast<u32x4s*>(dst + APL) = u32x4s{__float_as_uint(st.va[i][4]), __float_as_uint(st.va[i][5]),
+                                                         __float_as_uint(st.va[i][6]), __float_as_uint(st.va[i][7])};
+      } else {
+        put(As, APL, f % BM, f / BM, st.va[i], eA[st.sg]);
+      }
     }
 #pragma unroll
     for (int i = 0; i < BP; ++i) {
@@ -1066,9 +1116,20 @@ void launch_wg3_cfg(const WGradArgs& a, hipStream_t s) {
   if ((int64_t)a.dst.rows_per_split * (a.seg[0].lda > a.seg[0].ldb ? a.seg[0].lda : a.seg[0].ldb) * 4 >= (int64_t(1) << 30))
     throw std::runtime_error("split-bf16 wgrad: a split's rows exceed the 1 GiB buffer-descriptor range");
   dim3 grid((a.Ma + BM - 1) / BM, (a.Nb + BN - 1) / BN, a.dst.splits);
+  // planes: segment 0 of two, on the f16 split
+  if (a.nseg > 1 && a.seg[1].Ap.hi) throw std::runtime_error("split-f16 wgrad: only segment 0 takes planes");
+  if (a.seg[0].Ap.hi && (!a.f16 || a.nseg != 2 || !a.seg[0].Ap.lo || !a.seg[0].Ap.e || a.seg[0].lda != kPairLd ||
+                         a.Mpad > kPairLd))
+    throw std::runtime_error("split-f16 wgrad: plane operand needs the f16 split, two segments, both planes and 256 columns");
   WGradArgs b = a;
   b.low_seg = g_options.low_seg;
-  if (a.f16)
+  if (a.f16 && a.seg[0].Ap.hi) {
+    // (256 plane columns: the 256-row tile is the only one that meets them)
+    if constexpr (BM == kPairLd)
+      hipLaunchKernelGGL((wgrad3_kernel<WM, WN, TM, TN, OCC, 2, 2, true>), grid, dim3(WM * WN * 64), 0, s, b);
+    else
+      throw std::runtime_error("split-f16 wgrad: plane operand on a tile narrower than its 256 columns");
+  } else if (a.f16)
     hipLaunchKernelGGL((wgrad3_kernel<WM, WN, TM, TN, OCC, PF, 2>), grid, dim3(WM * WN * 64), 0, s, b);
   else
     hipLaunchKernelGGL((wgrad3_kernel<WM, WN, TM, TN, OCC, PF, 3>), grid, dim3(WM * WN * 64), 0, s, a);
@@ -1119,6 +1180,9 @@ void launch_rowgemm(const RowGemmArgs& a, hipStream_t s) {
 void launch_wgrad(const WGradArgs& a, hipStream_t s) {
   if (a.dst.splits <= 0) return;
   const int Mp = a.Ma, Np = a.Nb;
+  // a plane operand has no f32 form: only the split kernel reads it
+  if ((a.seg[0].Ap.hi || (a.nseg > 1 && a.seg[1].Ap.hi)) && (Np <= 128 || g_options.split_wg == 0))
+    throw std::runtime_error("wgrad: plane operand outside the split kernel");
   // output tile by (fan_in, fan_out); every B column set of one split lives in one block row
   if (Np <= 32) {
     if (Mp <= 64) launch_wg_cfg<2, 1, 1, 1>(a, s);          // 64 x 32

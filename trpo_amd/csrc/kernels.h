@@ -13,7 +13,7 @@ namespace trpo {
 // Kernel-variant switches (defaults from TRPO_SPLIT_MFMA, TRPO_SPLIT_WG, TRPO_CHAIN, TRPO_SPLIT_F16,
 // TRPO_SPLIT_MIN_K, TRPO_GRAPHS, TRPO_TAIL, TRPO_FUSED, TRPO_LOW_SEG, TRPO_PLANES, TRPO_RBWD0, TRPO_HBWD2,
 // TRPO_HEAD_FWD, TRPO_SPLITS, TRPO_PG_SPLITS, TRPO_LS_FUSED, TRPO_CG_FUSE_REDUCE, TRPO_CG_P_IMG, TRPO_RFWD01,
-// TRPO_FWD01 in gemm.hip, in the order of the fields; runtime-settable through trpo_set_option for A/B and
+// TRPO_FWD01, TRPO_RH1_PLANES in gemm.hip, in the order of the fields; runtime-settable through trpo_set_option for A/B and
 // parity tests).
 struct Options {
   int split_mfma;  // row GEMMs with N > 128 on the split MFMA: 0 off (f32 MFMA), 5 = 256 x 256 tile at
@@ -53,6 +53,10 @@ struct Options {
   int rfwd01;          // engine: the FVP's R-forward through layers 0 and 1 in one launch (rfwd.hip) where eligible
   int fwd01;           // engine: the prepare / line-search forward through layers 0 and 1 in one launch (rfwd.hip)
                        // (two hidden layers of 256, obs <= 128, the fused tail, X planes): 1 (default) on, 0 off
+  int rh1_planes;      // engine: under rfwd01 + rbwd0 on the f16 split, RH1 (per FVP, written by rfwd01) is kept as
+                       // row-paired f16 hi / lo planes (PairPlane below); its readers, the layer-1 weight gradient
+                       // and the fused R-backward's epilogue, fetch the hi plane alone where their low_seg test
+                       // fires and both planes where it does not: 1 (default) on, 0 off
 };
 
 // A running-max slot is kAmaxSub counters, each on its own 128-B line: producers reduce within the
@@ -194,12 +198,28 @@ struct SlabDst {
   int64_t off_w = 0, off_b = 0;
 };
 
+// Row-paired f16 planes of a [rows][256] operand (option rh1_planes): the dword at (row >> 1) * 256 + col holds
+// rows 2p (low half) and 2p + 1 (high half) of one column, value * 2^(*e) rounded toward zero (hi) and the f16 of
+// the exact remainder (lo).  A plane is pair_plane_dwords(rows) dwords; a row past the operand's last in the last
+// pair holds zeros.  Readers take 4 B per lane, 32 consecutive columns in one 128-B run.
+struct PairPlane {
+  const unsigned* hi = nullptr;   // NULL: no planes (the f32 operand is read)
+  const unsigned* lo = nullptr;
+  const int* e = nullptr;
+};
+constexpr int kPairLd = 256;   // columns of a paired plane
+constexpr int64_t pair_plane_dwords(int64_t rows) { return (rows + 1) / 2 * kPairLd; }
+
 struct WSeg {
   const float* A;  // [rows][lda]
   const float* B;  // [rows][ldb]
   int lda, ldb;
   const unsigned* amaxA = nullptr;   // f16 split: max |A|, max |B| (float bits; NULL = bounded by 1)
   const unsigned* amaxB = nullptr;
+  // f16 split: A as row-paired planes (lda = 256): staged straight into the LDS image, no f32 load and no split;
+  // on the one-product path the lo plane is not read.  The segment's A scale is 2^(*Ap.e); the low_seg test keeps
+  // reading amaxA.
+  PairPlane Ap{};
 };
 
 struct WGradArgs {
@@ -572,6 +592,9 @@ struct RBwd0Args {
   const float* H;           // [rows][Npad] H_1
   const float* E;           // [rows][Npad] E_0 (NULL: no E RH term)
   const float* RH;          // [rows][Npad] RH_1
+  // RH_1 as row-paired planes (Npad = 256): the epilogue reads the hi plane when the launch's low_seg test fires
+  // (whether or not A1h is attached), hi + lo otherwise; RH is then not read
+  PairPlane RHp{};
   const uint16_t* Xh;       // X's k-blocked f16 planes (GemmSeg::Ah layout), scale 2^(*eX)
   const uint16_t* Xl;
   int x_mpad, x_ldp;
@@ -642,6 +665,11 @@ struct Rfwd01Args {
   const float *H1, *c0, *c1;         // H1; the tangent biases of layers 0 and 1 (v + offb[l])
   const float* V0;                   // the direction's layer-0 block, [obs][256] (v + offW[0])
   float *RH1, *RZ2;
+  // set: RH1 is written as row-paired f16 planes into RH1's bytes (hi plane, then lo plane at
+  // pair_plane_dwords(n) dwords) at one launch-wide exponent from the bound |RH1| <= max_s |X_s|_2 max_j |V0_j|_2
+  // 1.01 + max |c0|, with max_s |X_s|_2 <= sqrt(obs) max |X| and max |X| < 2^(12 - *eX); workgroup 0 writes the
+  // exponent to *e_rh1
+  int* e_rh1 = nullptr;
   const uint16_t* img;               // rfwd01_img_bytes()
   const unsigned *am_v0, *am_w1, *am_v1;   // the images' running-max slots
   unsigned *am_rh1, *am_rz2;         // running max |RH1|, |RZ2| (atomicMax'd)
@@ -665,6 +693,9 @@ struct Fwd01Args {
 // of 64 bytes must stay under 2^31 (the engine takes the per-layer plane path beyond)
 constexpr bool rfwd01_rows_ok(int64_t x_mpad) { return 4 * x_mpad * 64 < (int64_t(1) << 31); }
 static_assert(rfwd01_rows_ok((1 << 23) - 256) && !rfwd01_rows_ok(1 << 23), "rfwd01 / fwd01 row limit");
+// the row-paired planes (option rh1_planes) are addressed per tile / per split from 64-bit bases, so they take
+// every row count the producer does: one limit, shared by the engine's gate and the launchers
+constexpr bool pair_planes_rows_ok(int64_t x_mpad) { return rfwd01_rows_ok(x_mpad); }
 bool fwd01_eligible(int L, const int* w, const int* wp);
 size_t fwd01_img_bytes();
 void launch_fwd01_img(const float* th, int64_t offW0, int64_t offW1, int obs, const unsigned* am_w0,

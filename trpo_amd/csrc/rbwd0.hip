@@ -26,6 +26,11 @@
 //     scale (the smaller of their running-max ones) on three products.  X from its planes' exponent; RD_0 per
 //     tile (workgroup max), the weight-gradient accumulator rescaled (exactly, by a power of two) whenever a
 //     tile needs a smaller exponent than the running one, and unscaled once at the end.
+//   * RH_1 as row-paired f16 planes (RBwd0Args::RHp, kernels.h PairPlane): the E_0 RH_1 term is an O(eps) KL_ff
+//     term like segment 1, so when that segment's low_seg test fires (rbwd0_one1: the same test, whether or not
+//     D_1's plane is attached) the epilogue reads RH_1's hi plane alone, 2 B per element instead of 4, and
+//     otherwise hi + lo (22 bits at the planes' one exponent).  A plane dword holds rows r, r + 1 of a column:
+//     the accumulator registers 2 i, 2 i + 1 of this lane, so a chunk of 4 registers takes 2 loads, not 4.
 #include "rowepi.h"
 #include <stdexcept>
 #include <type_traits>
@@ -139,7 +144,9 @@ __device__ __forceinline__ f32x16 mfma3h(const f16x8& ah, const f16x8& al, const
 // NSEG = 2: FVP ([RD_1 | D_1], with the E RH term); NSEG = 1: policy gradient (DS_1, no E term)
 // SW: segment 1 on one product from D_1's hi plane (decided per launch on the device, rbwd0_sw); the two
 // variants are separate instantiations so neither carries the other's live ranges
-template <int NSEG, bool SW>
+// RP: RH_1 from the f32 matrix (0), from its hi plane (1: the low_seg test fired, SW bodies) or (2: the bodies
+// without D_1's plane) from its hi plane where the test fired and from hi + lo where it did not, decided per launch
+template <int NSEG, bool SW, int RP>
 __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* smem, float* sMax) {
   constexpr bool kE = NSEG == 2;
   constexpr int TM = kR0TM, CT = kR0CT;
@@ -176,7 +183,6 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
   // 16-B load per thread and k-tile, half the bytes of f32 D_1). Its tiles run FIRST, at the plane's own
   // product scale 2^(eA1p + eB1); the accumulator then steps down to 2^eP (a power of two: exact) for
   // segment 0. Without the plane (or with a k-tile count the unrolled loop cannot split) both run 3 products.
-  (void)one1;
   constexpr int sw = SW ? 1 : 0;   // rbwd0_sw: one1 with the plane and an even split of the k-loop
   // the plane's scale: one exponent (*eA1p) or one per 32-row tile (eA1t, hbwd.hip: row tile tm of a 128-row
   // tile steps down by its own power of two)
@@ -430,14 +436,26 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
       auto mk = [&](const float* p) {
         return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (size_t)t0 * Npad), 0, tb, 0x00020000);
       };
-      const __amdgpu_buffer_rsrc_t rH = mk(A.H), rE = mk(kE ? A.E : A.H), rRH = mk(kE ? A.RH : A.H);
+      const __amdgpu_buffer_rsrc_t rH = mk(A.H), rE = mk(kE ? A.E : A.H), rRH = mk(kE && !RP ? A.RH : A.H);
+      // RH_1's planes: the tile's row pairs (t0 is even), sized to the real rows' pairs (Npad = kPairLd)
+      auto mkp = [&](const unsigned* p) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(p + (size_t)(t0 >> 1) * kPairLd), 0,
+                                                 (Mt + 1) / 2 * kPairLd * 4, 0x00020000);
+      };
+      const __amdgpu_buffer_rsrc_t rPh = RP ? mkp(A.RHp.hi) : rH, rPl = RP == 2 ? mkp(A.RHp.lo) : rH;
+      // uniform; the hi plane alone: the lo loads address past the descriptor (they read 0 and fetch nothing)
+      const bool lo2 = RP == 2 && !one1;
+      const float uR = RP ? __builtin_ldexpf(1.0f, -__builtin_amdgcn_readfirstlane(*A.RHp.e)) : 1.0f;
       // chunks of EC registers of one accumulator tile, the next LA chunks' loads in flight
       constexpr int EC = R0_EC, LA = kE ? R0_ELA : R0_ELA1;
+      static_assert(!RP || EC % 2 == 0, "a plane dword holds two accumulator registers");
+      // d[2]: RH_1 (RP 0), or the hi plane's dwords in [0, EC / 2) and the lo plane's in [EC / 2, EC) as bits
       float pre[LA + 1][3][EC];
       auto load_part = [&](int c, float (&d)[3][EC]) {
         constexpr int PPT = 16 / EC;   // chunks per accumulator tile
         const int tn = c % CT, tm = (c / CT) / PPT, hf = (c / CT) % PPT;
         const int vo = col0 + 32 * tn < Npad ? ((4 * lh) * Npad + col0 + 32 * tn + lr) * 4 : kOob;
+        const int vp = vo - ((vo >> 1) & (2 * kPairLd * 4));   // row pair 2 lh, not row 4 lh
 #pragma unroll
         for (int j = 0; j < EC; ++j) {
           const int r = EC * hf + j;
@@ -450,12 +468,29 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
           d[0][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rH, vo, so, 0));
           if constexpr (kE) {
             d[1][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rE, vo, so, 0));
-            d[2][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rRH, vo, so, 0));
+            if constexpr (RP == 0) {
+              d[2][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rRH, vo, so, 0));
+            } else if ((j & 1) == 0) {
+              // registers r, r + 1: rows 32 tm + (r & 3) + 8 (r >> 2) + 4 lh and the next, one pair
+              const int sp = (16 * tm + ((r & 3) >> 1) + 4 * (r >> 2)) * kPairLd * 4;
+              d[2][j >> 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rPh, vp, sp, 0));
+              if constexpr (RP == 2)
+                d[2][EC / 2 + (j >> 1)] =
+                    __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rPl, lo2 ? vp : kOob, sp, 0));
+            }
           } else {
             d[1][j] = 0.0f;
             d[2][j] = 0.0f;
           }
         }
+      };
+      // RH_1 of chunk register j from the planes' dwords: the f16 in the low (j even) or high half
+      auto plane_rh = [&](const float (&d)[3][EC], int j) {
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        auto half = [&](float w) { return (float)__builtin_bit_cast(h2, w)[j & 1]; };
+        float v = half(d[2][j >> 1]);
+        if constexpr (RP == 2) v += half(d[2][EC / 2 + (j >> 1)]);
+        return v * uR;
       };
       constexpr int NC = (16 / EC) * TM * CT;
 #pragma unroll
@@ -468,7 +503,10 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
 #pragma unroll
         for (int j = 0; j < EC; ++j) {
           const int r = EC * hf + j;
-          acc[tm][tn][r] = fmaf(op[1][j], op[2][j], acc[tm][tn][r] * one_minus_sq(op[0][j]));
+          float rhv;
+          if constexpr (kE && RP != 0) rhv = plane_rh(op, j);
+          else rhv = op[2][j];
+          acc[tm][tn][r] = fmaf(op[1][j], rhv, acc[tm][tn][r] * one_minus_sq(op[0][j]));
         }
         // no stores here to pin the loads: keep the scheduler from hoisting every chunk's loads
         __builtin_amdgcn_sched_barrier(0);
@@ -566,27 +604,40 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
   }
 }
 
-__device__ __forceinline__ bool rbwd0_sw(const RBwd0Args& A) {
-  if (kR0BK != 32 || A.nseg < 2 || !A.A1h || A.low_seg <= 0) return false;
-  const int nk = (A.K + kR0BK - 1) / kR0BK;
-  if (nk % R0_PF) return false;
+// the launch's low_seg verdict: segment 1 (and with it every O(eps) KL_ff operand) >= low_seg binades under
+__device__ __forceinline__ bool rbwd0_one1(const RBwd0Args& A) {
+  if (A.nseg < 2 || A.low_seg <= 0) return false;
   const int q0 = amax_exp(A.am_a0) + amax_exp(A.am_b0), q1 = amax_exp(A.am_a1) + amax_exp(A.am_b1);
   const int pen0 = (!A.am_a0 || !A.am_b0) ? 4 : 0;
   return __builtin_amdgcn_readfirstlane(q1 - q0 >= A.low_seg + pen0 ? 1 : 0) != 0;
 }
+// ... and segment 1's k-tiles can run on D_1's hi plane
+__device__ __forceinline__ bool rbwd0_sw(const RBwd0Args& A, bool one1) {
+  if (kR0BK != 32 || A.nseg < 2 || !A.A1h || A.low_seg <= 0) return false;
+  const int nk = (A.K + kR0BK - 1) / kR0BK;
+  if (nk % R0_PF) return false;
+  return one1;
+}
 
-template <int NSEG>
+// PL: RH_1 comes as planes (a kernel of its own: four bodies in one kernel doubled its scalar spills)
+template <int NSEG, bool PL = false>
 __global__ void __launch_bounds__(kR0NT, 1) rbwd0_kernel(const RBwd0Args A) {
   __shared__ __attribute__((aligned(16))) unsigned short smem[kR0LDSU];
   __shared__ float sMax[kR0NW];
   if (A.skip && *A.skip) return;
   if constexpr (NSEG > 1) {
-    if (rbwd0_sw(A)) {
-      rbwd0_body<NSEG, true>(A, smem, sMax);
+    const bool one1 = rbwd0_one1(A), sw = rbwd0_sw(A, one1);
+    if constexpr (PL) {
+      if (sw) rbwd0_body<NSEG, true, 1>(A, smem, sMax);
+      else rbwd0_body<NSEG, false, 2>(A, smem, sMax);
+      return;
+    }
+    if (sw) {
+      rbwd0_body<NSEG, true, 0>(A, smem, sMax);
       return;
     }
   }
-  rbwd0_body<NSEG, false>(A, smem, sMax);
+  rbwd0_body<NSEG, false, 0>(A, smem, sMax);
 }
 
 }  // namespace
@@ -605,6 +656,8 @@ void launch_rbwd0(const RBwd0Args& a, hipStream_t s) {
   if ((int64_t)a.dst.splits * a.dst.rows_per_split < a.rows) throw std::runtime_error("rbwd0: splits do not cover the rows");
   if (a.nseg != 1 && a.nseg != 2) throw std::runtime_error("rbwd0: nseg must be 1 or 2");
   if ((a.nseg == 2) != (a.E != nullptr)) throw std::runtime_error("rbwd0: the E RH term goes with two segments");
+  if (a.RHp.hi && (a.nseg != 2 || !a.RHp.lo || !a.RHp.e || a.Npad != kPairLd || a.dst.rows_per_split % 2))
+    throw std::runtime_error("rbwd0: RH_1 planes need two segments, both planes and 256 columns");
   RBwd0Args b = a;
   b.low_seg = g_options.low_seg;
   if (b.nseg == 1) {   // no absent operand is ever a null base: segment 1 aliases segment 0 (never read)
@@ -613,7 +666,8 @@ void launch_rbwd0(const RBwd0Args& a, hipStream_t s) {
     b.am_a1 = b.am_a0;
     b.am_b1 = b.am_b0;
   }
-  if (a.nseg == 2) hipLaunchKernelGGL(rbwd0_kernel<2>, dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
+  if (a.nseg == 2 && a.RHp.hi) hipLaunchKernelGGL((rbwd0_kernel<2, true>), dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
+  else if (a.nseg == 2) hipLaunchKernelGGL(rbwd0_kernel<2>, dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
   else hipLaunchKernelGGL(rbwd0_kernel<1>, dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
 }
 

@@ -162,7 +162,18 @@ __device__ __forceinline__ void rf_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned v
                : "v"(voff + soff), "s"(rsrc), "s"(lds));
 }
 
-template <int KS0>   // 16-deep k-steps over obs (obs <= 16 KS0)
+// PL (option rh1_planes): RH1 leaves as row-paired f16 hi / lo planes (kernels.h PairPlane) in the bytes of the f32
+// matrix, at one launch-wide exponent eR from a bound known before the first tile, |RH1| <= sqrt(obs) 2^(12 - eX)
+// max_j |V0_j|_2 1.01 + max |c0| (the per-state bound below with max_s |X_s|_2 <= sqrt(obs) max |X| and max |X| <
+// 2^(12 - eX), X's planes' exponent being f16_scale_exp of it; looser than the per-state bounds by at most
+// log2 sqrt(128) + 1 = 4.5 binades, free until a lo half leaves f16's range).  A plane dword holds rows 2p, 2p + 1
+// of one column and a lane holds one row, so lanes s, s ^ 1 exchange halves of a slice (one quad_perm DPP move per
+// value): the even lane then holds both rows of features 8 j + 4 h + i for j = 0, 1, the odd lane for j = 2, 3,
+// 4 consecutive dwords each: two 16-B stores per plane, the 4 store instructions per A chunk arrive() counts.
+// The split is rf_split8's (round toward zero, lo = the f16 of the exact remainder) at eR, not the A operand's
+// per-state one: a K-along-rows reader cannot carry a per-row scale.  When n is odd the last pair's odd row (past
+// n: it would hold (1 - 0) c0) is zeroed after the tile loop by the workgroup that stored it.
+template <int KS0, bool PL>   // 16-deep k-steps over obs (obs <= 16 KS0)
 __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Args a) {
   static_assert(!RF_ILV || KS0 == 8, "interleaved DMA: one instruction per k-step of phase A");
   // the ring: chunk c in slot c % 4.  An A chunk holds V0^T slice t (image units 0..1023) and H1 slice t of the
@@ -209,6 +220,17 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
     mc0 = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
     __syncthreads();   // red is reused by amax_commit3 at the end
   }
+  int eR = 0;   // the planes' exponent
+  if constexpr (PL) {
+    static_assert(RF_CSB, "the planes' exponent comes from the bound");
+    // max |X| < 2^(12 - eX): X's planes' exponent is f16_scale_exp of it
+    const float bnd = sqrtf((float)a.obs) * __builtin_ldexpf(1.0f, 12 - eX) * nv0 * 1.01f + mc0;
+    eR = __builtin_amdgcn_readfirstlane(f16_scale_exp(bnd));
+    if (blockIdx.x == 0 && tid == 0) *a.e_rh1 = eR;
+  }
+  const float scR = __builtin_ldexpf(1.0f, eR);
+  const bool odd = (s & 1) != 0;
+  const unsigned plane_lo = (unsigned)pair_plane_dwords(a.n);   // dwords (n < 2^23)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ordinary loads retired before the first DMA
   auto slot = [&](int k) -> cu32x4* { return k == 0 ? q0 : k == 1 ? q1 : k == 2 ? q2 : q3; };
   auto rows_of = [&](int64_t r0w) { return (int)(a.n - r0w < 32 ? (a.n - r0w > 0 ? a.n - r0w : 0) : 32); };
@@ -242,7 +264,8 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
   // visible, and every wave is past chunk c - 1, whose slot takes chunk c + 3's DMA next).  Completions retire in
   // issue order, so the wait is "at most the number of VMEM operations this wave issued after chunk c's DMA":
   // chunks c + 1 and c + 2's DMAs (8 + 8) and the 4 RH1 stores of the A chunk among c .. c + 2 = 20 (the first
-  // tile's A_0: only the two DMAs, 16).  Across a tile boundary more than 63 sit behind it (the X loads, the 128
+  // tile's A_0: only the two DMAs, 16).  The planes form stores the same number: 2 row-pair quads of the hi plane
+  // and 2 of the lo plane per A chunk are 4 store instructions, so every count here holds for both forms.  Across a tile boundary more than 63 sit behind it (the X loads, the 128
   // RZ2 stores): vmcnt(63) there, which also covers the next tile's X loads (128 stores were issued after them).
   // A smaller count than the true one only waits longer; none is larger.
   auto arrive = [&](bool far, bool first_a0) __attribute__((always_inline)) {
@@ -272,7 +295,9 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
       x[ks][1] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rxl, xlane, so, 0));
     }
   };
-  const unsigned hlane = (unsigned)(s * kRfLd + 4 * h) * 4u;   // RH1 rows: lane part of the offset
+  // RH1 rows: lane part of the offset (planes: row pair s >> 1, columns 16 (s & 1) + 4 h .. + 3 of the slice)
+  const unsigned hlane = PL ? (unsigned)((s >> 1) * kPairLd + 16 * (s & 1) + 4 * h) * 4u
+                            : (unsigned)(s * kRfLd + 4 * h) * 4u;
 
   f16x8 xt[KS0][2];   // X of this wave's 32 states, the whole tile
   xload((int64_t)blockIdx.x * kRfTile + wv * 32, xt);   // (grid <= tiles: a real tile)
@@ -293,7 +318,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
     const int64_t r0n = r0 + (int64_t)gridDim.x * kRfTile;     // ... in the next tile
     const int rows = rows_of(r0);
     const __amdgpu_buffer_rsrc_t rrh =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(a.RH1 + r0 * kRfLd), 0, rows * kRfLd * 4, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)(a.RH1 + r0 * kRfLd), 0, PL ? 0 : rows * kRfLd * 4, 0x00020000);
     f32x16 acc[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = f32x16{};
@@ -376,11 +401,43 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
             mt = fmaxf(mt, fabsf(rh[r]));
           }
         }
+        if constexpr (PL) {
+          // the wave's 16 row pairs of the hi plane, sized to the real rows' pairs, and of the lo plane plane_lo on
+          // (built here, per slice: across the slice loop their 8 scalar registers spilled)
+          float* const ph = a.RH1 + (r0 >> 1) * kPairLd;
+          int pbytes = (rows + 1) / 2 * kPairLd * 4;
+          asm volatile("" : "+s"(pbytes));   // not hoisted out of the slice loop
+          const __amdgpu_buffer_rsrc_t rph = __builtin_amdgcn_make_buffer_rsrc((void*)ph, 0, pbytes, 0x00020000);
+          const __amdgpu_buffer_rsrc_t rpl =
+              __builtin_amdgcn_make_buffer_rsrc((void*)(ph + plane_lo), 0, pbytes, 0x00020000);
+          // this lane's 8 columns: registers i (even lane) or 8 + i (odd lane) of both rows of the pair; one quad
+          // of columns at a time (the scheduling barrier keeps 8 packed dwords live, not 16)
 #pragma unroll
-        for (int j = 0; j < 4 && (RF_ABL & 8) == 0; ++j)
-          __builtin_amdgcn_raw_buffer_store_b128(
-              __builtin_bit_cast(cu32x4, f32x4{rh[4 * j], rh[4 * j + 1], rh[4 * j + 2], rh[4 * j + 3]}), rrh, hlane,
-              (32 * t + 8 * j) * 4, 0);
+          for (int j = 0; j < 2; ++j) {
+            cu32x4 Hq, Lq;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int i = 4 * j + q;
+              const float nl = dpp_f<kDppX1>(rh[i]), nh = dpp_f<kDppX1>(rh[8 + i]);
+              const float ev = (odd ? nh : rh[i]) * scR, od = (odd ? rh[8 + i] : nl) * scR;
+              const rf_h2 hp = __builtin_amdgcn_cvt_pkrtz(ev, od);
+              const rf_h2 lp = __builtin_amdgcn_cvt_pkrtz(ev - (float)hp[0], od - (float)hp[1]);
+              Hq[q] = __builtin_bit_cast(unsigned, hp);
+              Lq[q] = __builtin_bit_cast(unsigned, lp);
+            }
+            if constexpr ((RF_ABL & 8) == 0) {
+              __builtin_amdgcn_raw_buffer_store_b128(Hq, rph, hlane, (32 * t + 8 * j) * 4, 0);
+              __builtin_amdgcn_raw_buffer_store_b128(Lq, rpl, hlane, (32 * t + 8 * j) * 4, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4 && (RF_ABL & 8) == 0; ++j)
+            __builtin_amdgcn_raw_buffer_store_b128(
+                __builtin_bit_cast(cu32x4, f32x4{rh[4 * j], rh[4 * j + 1], rh[4 * j + 2], rh[4 * j + 3]}), rrh, hlane,
+                (32 * t + 8 * j) * 4, 0);
+        }
         mR = fmaxf(mR, mt);
         if constexpr ((RF_ABL & 64) == 0 && !RF_CSB) mt = xmax_f<true>(mt);   // the state's max over the slice
         const int Pt = (RF_ABL & 64) ? 2 : min(mt > 0.0f ? f16_scale_exp(mt) + eW : 1000, f16_scale_exp(1.0f) + eV);
@@ -481,6 +538,18 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no DMA may land after the workgroup has left the CU
+  if constexpr (PL) {
+    // n odd: the high halves of the last pair, in both planes, behind this workgroup's own stores to them (every
+    // wave's stores have completed: the wait above, then the barrier)
+    if ((a.n & 1) != 0 && (int64_t)blockIdx.x == (ntiles - 1) % (int64_t)gridDim.x) {
+      __syncthreads();
+      int col = threadIdx.x;
+      asm volatile("" : "+v"(col));   // the address is formed here, not carried across the tile loop
+      unsigned short* const p = reinterpret_cast<unsigned short*>(a.RH1 + (a.n >> 1) * kPairLd + col) + 1;
+      p[0] = 0;
+      p[2 * pair_plane_dwords(a.n)] = 0;
+    }
+  }
   amax_commit3<true>(a.am_rh1, mR, a.am_rz2, mZ, nullptr, 0.0f, red);
 }
 
@@ -719,7 +788,12 @@ void launch_rfwd01(const Rfwd01Args& a, int num_cus, hipStream_t s) {
     throw std::runtime_error("rfwd01: X plane geometry");
   const int64_t ntiles = (a.n + kRfTile - 1) / kRfTile;
   const int grid = (int)std::min<int64_t>(ntiles, (int64_t)num_cus);
-  hipLaunchKernelGGL(rfwd01_kernel<8>, dim3(grid), dim3(kRfWaves * 64), 0, s, a);
+  if (a.e_rh1) {
+    if (!pair_planes_rows_ok(a.x_mpad)) throw std::runtime_error("rfwd01: RH1 plane geometry");
+    hipLaunchKernelGGL((rfwd01_kernel<8, true>), dim3(grid), dim3(kRfWaves * 64), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((rfwd01_kernel<8, false>), dim3(grid), dim3(kRfWaves * 64), 0, s, a);
+  }
 }
 
 bool fwd01_eligible(int L, const int* w, const int* wp) { return rfwd01_eligible(L, w, wp); }

@@ -139,8 +139,17 @@ static int* option_slot(const std::string& k) {
   if (k == "cg_fuse_reduce") return &g_options.cg_fuse_reduce;
   if (k == "rfwd01") return &g_options.rfwd01;
   if (k == "fwd01") return &g_options.fwd01;
+  if (k == "rh1_planes") return &g_options.rh1_planes;
   if (k == "cg_p_img") return &g_options.cg_p_img;
   throw ArgError("unknown option " + k);
+}
+
+int trpo_plane_rows_ok(int64_t x_mpad, int* rfwd01_ok, int* pair_planes_ok) {
+  return guarded([&] {
+    REQUIRE(rfwd01_ok && pair_planes_ok, "NULL argument");
+    *rfwd01_ok = rfwd01_rows_ok(x_mpad) ? 1 : 0;
+    *pair_planes_ok = pair_planes_rows_ok(x_mpad) ? 1 : 0;
+  });
 }
 
 int trpo_set_option(const char* name, int value) {
