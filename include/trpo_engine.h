@@ -296,15 +296,54 @@ int trpo_profile_reset(trpo_engine* e);
  * max_pathlength cut off.  The rollout records it per path, with the state s_T after the last step and
  * the policy's distribution there (trpo_rollout_fetch_ends), so that GAE can bootstrap cut-off paths
  * from V(s_T) (trpo_get_tail_view, trpo_vf_predict_tails).  The per-step outputs and the random
- * draws do not depend on it. */
+ * draws do not depend on it.
+ *
+ * Two more of gym's discrete-action classic_control tasks, which the reference does not run, roll out the same way
+ * (trpo_rollout_env).  gym is not vendored: the equations below are the definition.  All arithmetic is float64
+ * in the operation order written (x^2 is x*x), pi = 3.141592653589793, min/max as Python's.
+ *
+ * MountainCar-v0: state = obs = (p, v); actions 0, 1, 2; time limit 200.
+ *   reset: p = -0.6 + (-0.4 - -0.6)*u0, v = 0 (one draw)
+ *   step:  v = v + (action-1)*0.001 + cos(3*p)*(-0.0025);  v = min(max(v,-0.07),0.07)
+ *          p = p + v;  p = min(max(p,-1.2),0.6);  if (p == -1.2 && v < 0) v = 0
+ *          done = p >= 0.5 && v >= 0;  reward -1 on every step, the terminating one included
+ * Acrobot-v1 ("book" dynamics): state (t1, t2, w1, w2); obs (cos t1, sin t1, cos t2, sin t2, w1, w2); actions
+ * 0, 1, 2; time limit 500.
+ *   reset: s_i = -0.1 + (0.1 - -0.1)*u_i (four draws)
+ *   step:  torque a = action - 1; m1 = m2 = l1 = 1, lc1 = lc2 = 0.5, I1 = I2 = 1, g = 9.8, dt = 0.2;
+ *          f(t1,t2,w1,w2) = (w1, w2, dd1, dd2) with
+ *            d1   = m1*lc1^2 + m2*(l1^2 + lc2^2 + 2*l1*lc2*cos(t2)) + I1 + I2
+ *            d2   = m2*(lc2^2 + l1*lc2*cos(t2)) + I2
+ *            phi2 = m2*lc2*g*cos(t1 + t2 - pi/2)
+ *            phi1 = -m2*l1*lc2*w2^2*sin(t2) - 2*m2*l1*lc2*w2*w1*sin(t2) + (m1*lc1 + m2*l1)*g*cos(t1 - pi/2) + phi2
+ *            dd2  = (a + d2/d1*phi1 - m2*l1*lc2*w1^2*sin(t2) - phi2) / (m2*lc2^2 + I2 - d2^2/d1)
+ *            dd1  = -(d2*dd2 + phi1)/d1
+ *          one classical RK4 step: k1 = f(y), k2 = f(y + dt/2*k1), k3 = f(y + dt/2*k2), k4 = f(y + dt*k3),
+ *            y' = y + dt/6*(k1 + 2*k2 + 2*k3 + k4)
+ *          then t1, t2 wrapped into [-pi, pi] (while x > pi: x -= 2*pi; while x < -pi: x += 2*pi), w1 clamped to
+ *          +-4 pi and w2 to +-9 pi with min(max()); done = -cos(t1) - cos(t2 + t1) > 1.0 on the new state;
+ *          reward = done ? 0 : -1
+ * Reset draws are Philox (seed, env index, stream 1, episode*reset_draws + i), action draws (seed, env index,
+ * stream 0, step count), for every environment. */
+#define TRPO_ENV_CARTPOLE_V0 0
+#define TRPO_ENV_MOUNTAINCAR_V0 1
+#define TRPO_ENV_ACROBOT_V1 2
+typedef struct trpo_env_info_t {
+  int obs_dim, state_dim, n_actions;
+  int reset_draws;           /* uniforms one env.reset() consumes */
+  int time_limit;            /* the task's TimeLimit */
+  char name[32];
+} trpo_env_info_t;
+/* Host-only (works with no GPU): the table of a built-in environment; an unknown id is TRPO_ERR_ARG. */
+int trpo_env_info(int env, trpo_env_info_t* out);
 typedef struct trpo_rollout_params {
   int n_envs;                /* parallel environments (1) */
   int max_pathlength;        /* config["max_steps"] = 1000 (trpo_inksci.py:17; utils.py:28) */
   int64_t n_timesteps;       /* config["episodes_per_roll"] = 1000 (trpo_inksci.py:17; utils.py:23) */
   int train;                 /* 1: cat_sample; 0: argmax (trpo_inksci.py:79-83) */
-  int time_limit;            /* CartPole-v0's TimeLimit: 200 steps */
+  int time_limit;            /* the TimeLimit: CartPole-v0's 200 steps by default */
   uint64_t seed;             /* Philox stream: action uniforms and env.reset draws */
-  /* optional injected uniforms (tests): reset [n_envs][max_episodes_per_env][4] in [0,1) and
+  /* optional injected uniforms (tests): reset [n_envs][max_episodes_per_env][reset_draws] in [0,1) and
    * cat_sample [n_envs][ceil(n_timesteps/n_envs) + min(max_pathlength, time_limit) - 1] */
   const double* reset_uniforms;
   const double* action_uniforms;
@@ -314,7 +353,16 @@ typedef struct trpo_rollout_params {
 void trpo_default_rollout_params(trpo_rollout_params* p);
 /* run the rollout; returns the total steps N and the number of paths */
 int trpo_rollout_cartpole(trpo_engine* e, const trpo_rollout_params* p, int64_t* n_steps_out, int64_t* n_paths_out);
-/* the concatenated paths (utils.py:36-39): obs [N][4] f64 (and/or as the float32 the placeholders
+/* trpo_default_rollout_params with the environment's own time_limit */
+int trpo_default_rollout_params_env(int env, trpo_rollout_params* p);
+/* The same rollout of environment `env` (TRPO_ENV_*); trpo_rollout_cartpole is env = TRPO_ENV_CARTPOLE_V0.  The
+ * engine's obs_dim and n_actions must be the environment's: TRPO_ERR_ARG otherwise, with both in the message. */
+int trpo_rollout_env(trpo_engine* e, int env, const trpo_rollout_params* p, int64_t* n_steps_out,
+                     int64_t* n_paths_out);
+/* the environment state every observation was made from, concatenated like obs: [N][state_dim] f64 (for
+ * CartPole-v0 and MountainCar-v0 the observation itself).  TRPO_ERR_STATE when there is no rollout. */
+int trpo_rollout_fetch_states(trpo_engine* e, double* env_states, int mem);
+/* the concatenated paths (utils.py:36-39): obs [N][obs_dim] f64 (and/or as the float32 the placeholders
  * receive), actions [N] i64, action_dists [N][A] f32, rewards [N] f64, episode_starts [N] u8, and the
  * cat_sample uniform of every step; any may be NULL */
 int trpo_rollout_fetch(trpo_engine* e, double* obs, float* obs32, int64_t* actions, float* action_dists,
@@ -322,7 +370,7 @@ int trpo_rollout_fetch(trpo_engine* e, double* obs, float* obs32, int64_t* actio
 /* How each of the rollout's n_paths paths ended, in the order of the concatenated rollout: truncated
  * [n_paths] u8 (1 = the path's last step did not terminate the environment: time_limit or
  * max_pathlength cut it off; a step that terminates and reaches the limit counts as terminated),
- * final_obs [n_paths][obs_dim] f64 (s_T, the state after the last step), final_dists [n_paths][A] f32
+ * final_obs [n_paths][obs_dim] f64 (the observation of s_T, the state after the last step), final_dists [n_paths][A] f32
  * (the policy at float32(s_T) for cut-off paths, zeros for terminated ones), lengths [n_paths] i64 (T)
  * and end_rows [n_paths] i64 (the row of the path's last step); any may be NULL.  TRPO_ERR_STATE
  * when there is no rollout. */
@@ -377,6 +425,11 @@ int trpo_cat_sample(const float* prob, int64_t n, int k, const double* uniforms,
 /* one CartPole-v0 step per row (state [n][4] f64, action [n] i64); done = termination (not the TimeLimit) */
 int trpo_cartpole_step(const double* state, const int64_t* action, int64_t n, double* state_out, double* reward,
                        uint8_t* done, int mem);
+/* one step per row of environment `env`: state [n][state_dim] f64, action [n] i64 -> state_out [n][state_dim],
+ * obs_out [n][obs_dim] (the observation of state_out), reward [n], done [n] (termination, not the TimeLimit);
+ * any output may be NULL.  Engine-free, current device. */
+int trpo_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out, double* obs_out,
+                  double* reward, uint8_t* done, int mem);
 
 /* ==== value-function baseline: class VF (utils.py:48-92) ==================================
  * Features [obs | action_dist | t/10] (VF._features, utils.py:70-77) -> fully_connected(64, relu)

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 static int fails = 0;
@@ -93,6 +94,21 @@ int main() {
   CHECK_ERR(trpo_comm_init(nullptr, nullptr, 0, 1), TRPO_ERR_ARG);
   CHECK_ERR(trpo_comm_set_host_allreduce(nullptr, allreduce, nullptr, 0, 1), TRPO_ERR_ARG);
   CHECK_ERR(trpo_rollout_cartpole(nullptr, &rp, nullptr, nullptr), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_env(nullptr, TRPO_ENV_ACROBOT_V1, &rp, nullptr, nullptr), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_fetch_states(nullptr, nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  trpo_env_info_t ei;
+  CHECK(trpo_env_info(TRPO_ENV_ACROBOT_V1, &ei) == TRPO_OK && ei.obs_dim == 6 && ei.state_dim == 4 &&
+        ei.n_actions == 3 && ei.reset_draws == 4 && ei.time_limit == 500 && std::string(ei.name) == "Acrobot-v1");
+  CHECK(trpo_env_info(TRPO_ENV_MOUNTAINCAR_V0, &ei) == TRPO_OK && ei.obs_dim == 2 && ei.time_limit == 200);
+  CHECK_ERR(trpo_env_info(3, &ei), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_env_info(TRPO_ENV_CARTPOLE_V0, nullptr), TRPO_ERR_ARG);
+  CHECK(trpo_default_rollout_params_env(TRPO_ENV_ACROBOT_V1, &rp) == TRPO_OK && rp.time_limit == 500);
+  CHECK_ERR(trpo_default_rollout_params_env(-1, &rp), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_default_rollout_params_env(TRPO_ENV_CARTPOLE_V0, nullptr), TRPO_ERR_ARG);
+  trpo_default_rollout_params(&rp);
+  CHECK_ERR(trpo_env_step(5, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_env_step(TRPO_ENV_ACROBOT_V1, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST),
+            TRPO_ERR_ARG);
   CHECK_ERR(trpo_rollout_to_batch(nullptr, 1), TRPO_ERR_ARG);
   trpo_feed_view fv;
   CHECK_ERR(trpo_get_feed_view(nullptr, &fv), TRPO_ERR_ARG);

@@ -44,6 +44,14 @@ class RolloutParams(ctypes.Structure):
                 ("action_uniforms", c_void_p), ("max_episodes_per_env", c_int), ("mem", c_int)]
 
 
+ENV_CARTPOLE_V0, ENV_MOUNTAINCAR_V0, ENV_ACROBOT_V1 = range(3)
+
+
+class EnvInfo(ctypes.Structure):
+    _fields_ = [("obs_dim", c_int), ("state_dim", c_int), ("n_actions", c_int), ("reset_draws", c_int),
+                ("time_limit", c_int), ("name", ctypes.c_char * 32)]
+
+
 class CommInfo(ctypes.Structure):
     _fields_ = [("transport", c_int), ("rank", c_int), ("world", c_int), ("comm_count", c_int),
                 ("comm_rank", c_int), ("comm_device", c_int), ("device", c_int), ("pci_bus_id", ctypes.c_char * 64)]
@@ -112,6 +120,11 @@ SIGNATURES = {
     # sampling / rollouts (trpo_inksci.py:76-87, utils.py:18-45,95-105)
     "trpo_default_rollout_params": (None, [POINTER(RolloutParams)]),
     "trpo_rollout_cartpole": (c_int, [c_void_p, POINTER(RolloutParams), POINTER(c_int64), POINTER(c_int64)]),
+    "trpo_env_info": (c_int, [c_int, POINTER(EnvInfo)]),
+    "trpo_default_rollout_params_env": (c_int, [c_int, POINTER(RolloutParams)]),
+    "trpo_rollout_env": (c_int, [c_void_p, c_int, POINTER(RolloutParams), POINTER(c_int64), POINTER(c_int64)]),
+    "trpo_rollout_fetch_states": (c_int, [c_void_p, c_void_p, c_int]),
+    "trpo_env_step": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "trpo_rollout_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int]),
     "trpo_rollout_fetch_ends": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),

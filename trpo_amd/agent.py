@@ -11,7 +11,7 @@ Two ways to run one policy update, both on the GPU:
   ``trpo_inksci.py`` looks like once its TF session is replaced.
 
 * :meth:`TRPOAgent.learn` — the whole loop of ``trpo_inksci.py:89-177`` on the
-  device: CartPole-v0 rollouts (``rollout.hip``), VF baselines and fit
+  device: rollouts of ``config["env"]`` (CartPole-v0 by default; ``rollout.hip``), VF baselines and fit
   (``vf.hip``), advantages, the update, explained variance and the reference's
   stop rules; only the print-out statistics come back to the host.
 
@@ -22,7 +22,7 @@ For the update methods, paths come in as the reference's dicts
 ``config["gae_lambda"]`` (not in the reference) switches the advantages of all three
 from ``discount(rewards) - baseline`` to GAE(lambda); paths may then carry a
 ``"tail_value"`` scalar, V(s_T) of a path that was cut off rather than terminated.
-learn() keeps CartPole-v0's time limit as a termination, as the reference does, unless
+learn() keeps the environment's time limit as a termination, as the reference does, unless
 ``config["bootstrap_truncated"]`` is true (it needs ``gae_lambda``): the rollout then tells cut-off paths from
 terminated ones, and from the VF's first fit on the scan bootstraps every cut-off path from V(s_T).
 """
@@ -34,7 +34,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .engine import Engine, UpdateParams
+from .engine import Engine, UpdateParams, env_info
 from .vf import VF
 from .utils import (EngineLoss, GetFlat, KLFirstFixedGVP, SetFromFlat, SurrogateLoss, conjugate_gradient,
                     flatgrad, linesearch)
@@ -44,6 +44,11 @@ CONFIG = {"max_steps": 1000, "episodes_per_roll": 1000, "gamma": 0.95, "cg_dampi
 # An optional "gae_lambda" key (absent or None here: the reference's discount(rewards) - baseline) selects
 # GAE(lambda) advantages on the engine, with the VF's baseline as V.  With it, an optional
 # "bootstrap_truncated": True makes learn() bootstrap paths cut off by the time limit or max_steps from V(s_T).
+# Two more optional keys, neither in the reference: "env" (default "CartPole-v0"), the built-in environment
+# learn() rolls out (trpo_amd.engine.ENVS), and "reward_target" (default the reference's 1.1*500), the mean
+# episode reward above which learn() stops training.
+DEFAULT_ENV = "CartPole-v0"
+REWARD_TARGET = 1.1 * 500   # trpo_inksci.py:135
 
 
 class Session:
@@ -122,6 +127,17 @@ class TRPOAgent:
         if self.bootstrap_truncated and self.config.get("gae_lambda") is None:
             raise ValueError("config['bootstrap_truncated'] needs config['gae_lambda']: the reference's "
                              "returns - baseline estimator takes no tail values")
+        self.env = self.config.get("env", DEFAULT_ENV)
+        self.env_info = env_info(self.env)
+        # A config that names its environment must fit it.  Without the key the agent may be one that only
+        # updates from given paths, of any shape; learn() then refuses the default environment if it does not fit.
+        self.env_mismatch = None
+        if (int(obs_dim), int(n_actions)) != (self.env_info["obs_dim"], self.env_info["n_actions"]):
+            self.env_mismatch = (f"{self.env} has obs_dim {self.env_info['obs_dim']} and "
+                                 f"{self.env_info['n_actions']} actions; the agent was given obs_dim {obs_dim} "
+                                 f"and {n_actions} actions")
+            if "env" in self.config:
+                raise ValueError("config['env']: " + self.env_mismatch)
         self.engine = Engine(obs_dim, hidden, n_actions, max_rows, device)
         self.session = Session(self.engine, reinit_policy=reinit_policy)
         self.gf = GetFlat(self.session)                          # trpo_inksci.py:71
@@ -225,10 +241,10 @@ class TRPOAgent:
     def learn(self, max_iterations: Optional[int] = None, n_envs: int = 1, seed: int = 1,
               log: Optional[Callable[[str], None]] = print,
               draws: Optional[Callable[[int], tuple]] = None, record: bool = False) -> List[dict]:
-        """The reference's learn() loop on CartPole-v0, device-resident.  Stop rules as
-        trpo_inksci.py:131-141,172-175: training stops when the mean episode reward exceeds
-        1.1*500 or the baseline explains > 0.8 of the returns' variance; the loop then keeps
-        rolling out the argmax policy and ends after 100 such iterations; a NaN entropy ends it
+        """The reference's learn() loop on config["env"] (CartPole-v0 unless set), device-resident.  Stop rules
+        as trpo_inksci.py:131-141,172-175: training stops when the mean episode reward exceeds
+        config["reward_target"] (the reference's 1.1*500 unless set) or the baseline explains > 0.8 of the
+        returns' variance; the loop then keeps rolling out the argmax policy and ends after 100 such iterations; a NaN entropy ends it
         (the reference calls exit(-1)).  max_iterations bounds the loop (None: as the reference).
         draws(i) -> (reset_uniforms, action_uniforms, max_episodes_per_env) injects the random draws
         of iteration i's rollout (env.reset and cat_sample; tests), else a Philox stream per iteration.
@@ -238,11 +254,14 @@ class TRPOAgent:
         Returns one stats dict per iteration."""
         cfg = self.config
         eng = self.engine
+        if self.env_mismatch:
+            raise ValueError("learn(): " + self.env_mismatch + "; name the environment in config['env']")
+        reward_target = cfg.get("reward_target", REWARD_TARGET)
         # this rank's share of the timestep budget (trpo_inksci.py:96-100 over `world` ranks)
         n_timesteps = -(-cfg["episodes_per_roll"] // self.world)
         # worst case rows of one rollout: every environment overshoots its budget by one episode
         budget = -(-n_timesteps // n_envs)
-        worst = n_envs * (budget + min(cfg["max_steps"], 200) - 1)
+        worst = n_envs * (budget + min(cfg["max_steps"], self.env_info["time_limit"]) - 1)
         if worst > eng.max_rows:
             raise ValueError(f"learn(): a rollout of {n_envs} environments can reach {worst} steps, more than "
                              f"max_rows={eng.max_rows}; create the agent with max_rows >= {worst}")
@@ -257,10 +276,10 @@ class TRPOAgent:
             if draws is not None:
                 ru, au, me = draws(i)
                 inj = {"reset_uniforms": ru, "action_uniforms": au, "max_episodes_per_env": me}
-            n, n_paths = eng.rollout_cartpole(n_envs=n_envs, n_timesteps=n_timesteps,
-                                              max_pathlength=cfg["max_steps"],
-                                              seed=rollout_seed(seed, i, self.rank),
-                                              train=self.train, **inj)                   # :96-100
+            n, n_paths = eng.rollout(self.env, n_envs=n_envs, n_timesteps=n_timesteps,
+                                     max_pathlength=cfg["max_steps"],
+                                     seed=rollout_seed(seed, i, self.rank),
+                                     train=self.train, **inj)                            # :96-100
             n_global = int(self._host_sum(n)[0])
             eng.rollout_to_batch(n_global=n_global)                                      # :108-122
             have_base = self.vf.predict_engine(eng)                                      # :103
@@ -285,7 +304,7 @@ class TRPOAgent:
             if record:
                 rec.update({"rollout": eng.rollout_fetch(), "baseline": rb, "returns": r_ret, "advantages": r_adv,
                             "ends": eng.rollout_fetch_ends(), "tail_values": r_tail})
-            if reward_mean > 1.1 * 500:                                                  # :135-136
+            if reward_mean > reward_target:                                              # :135-136
                 self.train = False
             rec["train"] = self.train                    # whether this iteration updates the policy
             if not self.train:                                                           # :137-141

@@ -299,6 +299,8 @@ struct trpo_engine {
     int64_t rows = 0;      // capacity in region rows
     int envs = 0;
     double* obs = nullptr;
+    double* env_state = nullptr;   // [rows][state_cap]; only for an environment whose observation is not its state
+    int state_cap = 0;
     int64_t* actions = nullptr;
     float* dist = nullptr;
     double* rewards = nullptr;
@@ -653,11 +655,18 @@ struct trpo_engine {
     return static_cast<T*>(ptr);
   }
 
-  // rollout (utils.py:18-45) of n_envs CartPole-v0 instances under the current policy
-  void rollout(const trpo_rollout_params& p) {
+  // rollout (utils.py:18-45) of n_envs instances of a built-in environment under the current policy
+  void rollout(int env, const trpo_rollout_params& p) {
+    EnvDims ed{};
+    REQUIRE(env_dims(env, &ed), "unknown environment id " + std::to_string(env));
     REQUIRE(p.n_envs >= 1 && p.n_envs <= (1 << 20), "n_envs out of range");
     REQUIRE(p.n_timesteps >= 1 && p.max_pathlength >= 1 && p.time_limit >= 1, "bad rollout lengths");
-    REQUIRE(w[0] == 4 && w[L] == 2, "CartPole-v0 needs obs_dim 4 and 2 actions");
+    REQUIRE(w[0] == ed.obs_dim && w[L] == ed.n_actions,
+            std::string(ed.name) + " needs obs_dim " + std::to_string(ed.obs_dim) + " and " +
+                std::to_string(ed.n_actions) + " actions; the engine has obs_dim " + std::to_string(w[0]) + " and " +
+                std::to_string(w[L]) + " actions");
+    const int obs_dim = ed.obs_dim, A = ed.n_actions;
+    const int state_cap = ed.state_dim == ed.obs_dim ? 0 : ed.state_dim;   // such environments observe the state itself
     const int ep_max = std::min(p.max_pathlength, p.time_limit);
     const int64_t budget = (p.n_timesteps + p.n_envs - 1) / p.n_envs;
     const int64_t env_cap = budget + ep_max - 1;
@@ -665,25 +674,27 @@ struct trpo_engine {
     REQUIRE(rows <= (int64_t(1) << 34), "rollout too large");
     const int64_t paths = budget * p.n_envs;   // every episode has at least one step
     feed_is_rollout = false;                   // the end records of the loaded feed are about to be overwritten
-    if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths) {
+    if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths || state_cap > roll.state_cap) {
       for (void* ptr : roll.mem) HIPCHECK(hipFree(ptr));
       roll = RollBufs{};
       roll.rows = rows;
       roll.envs = p.n_envs;
       roll.paths = paths;
       roll.end_truncated = ralloc<uint8_t>(paths);
-      roll.end_obs = ralloc<double>((size_t)paths * 4);
-      roll.end_dist = ralloc<float>((size_t)paths * 2);
+      roll.end_obs = ralloc<double>((size_t)paths * obs_dim);
+      roll.end_dist = ralloc<float>((size_t)paths * A);
       roll.end_len = ralloc<int64_t>(paths);
       roll.end_row = ralloc<int64_t>(paths);
       roll.cat_truncated = ralloc<uint8_t>(paths);
-      roll.cat_obs32 = ralloc<float>((size_t)paths * 4);
-      roll.cat_dist = ralloc<float>((size_t)paths * 2);
+      roll.cat_obs32 = ralloc<float>((size_t)paths * obs_dim);
+      roll.cat_dist = ralloc<float>((size_t)paths * A);
       roll.cat_len = ralloc<int64_t>(paths);
       roll.cat_rows = ralloc<int64_t>(paths);
-      roll.obs = ralloc<double>((size_t)rows * 4);
+      roll.obs = ralloc<double>((size_t)rows * obs_dim);
+      roll.state_cap = state_cap;
+      if (state_cap) roll.env_state = ralloc<double>((size_t)rows * state_cap);
       roll.actions = ralloc<int64_t>(rows);
-      roll.dist = ralloc<float>((size_t)rows * 2);
+      roll.dist = ralloc<float>((size_t)rows * A);
       roll.rewards = ralloc<double>(rows);
       roll.starts = ralloc<uint8_t>(rows);
       roll.uniforms = ralloc<double>(rows);
@@ -692,6 +703,8 @@ struct trpo_engine {
       roll.offsets = ralloc<int64_t>((size_t)2 * p.n_envs);
     }
     RolloutArgs a{};
+    a.env = env;
+    a.state_dim = ed.state_dim;
     a.ps = policy_shape();
     a.theta = theta;
     a.maxw = max_width();
@@ -703,7 +716,7 @@ struct trpo_engine {
     a.env_cap = env_cap;
     a.max_episodes = p.max_episodes_per_env;
     a.seed = p.seed;
-    // optional injected uniforms (tests): reset [n_envs][max_episodes][4], act [n_envs][env_cap]
+    // optional injected uniforms (tests): reset [n_envs][max_episodes][reset_draws], act [n_envs][env_cap]
     auto stage_u = [&](const double* src, int64_t count, double*& buf, int64_t& cap_n) -> const double* {
       if (!src) return nullptr;
       if (p.mem == TRPO_MEM_DEVICE) return src;
@@ -715,14 +728,15 @@ struct trpo_engine {
       return buf;
     };
     if (p.reset_uniforms) REQUIRE(p.max_episodes_per_env >= 1, "max_episodes_per_env required with reset_uniforms");
-    a.reset_u = stage_u(p.reset_uniforms, (int64_t)p.n_envs * std::max(1, p.max_episodes_per_env) * 4, roll.reset_u,
-                        roll.reset_u_n);
+    a.reset_u = stage_u(p.reset_uniforms, (int64_t)p.n_envs * std::max(1, p.max_episodes_per_env) * ed.reset_draws,
+                        roll.reset_u, roll.reset_u_n);
     a.act_u = stage_u(p.action_uniforms, rows, roll.act_u, roll.act_u_n);
     if (a.reset_u) {
       // every episode an environment can start must have its uniforms
       REQUIRE((int64_t)p.max_episodes_per_env >= budget, "max_episodes_per_env must be >= ceil(n_timesteps/n_envs)");
     }
     a.obs = roll.obs;
+    a.env_state = state_cap ? roll.env_state : nullptr;
     a.actions = roll.actions;
     a.dist = roll.dist;
     a.rewards = roll.rewards;
@@ -2497,13 +2511,33 @@ int trpo_update(trpo_engine* e, const trpo_update_params* p, trpo_update_stats* 
   });
 }
 
-int trpo_rollout_cartpole(trpo_engine* e, const trpo_rollout_params* p, int64_t* n_steps_out, int64_t* n_paths_out) {
+int trpo_rollout_env(trpo_engine* e, int env, const trpo_rollout_params* p, int64_t* n_steps_out,
+                     int64_t* n_paths_out) {
   return guarded([&] {
     REQUIRE(e && p, "NULL argument");
     e->use();
-    e->rollout(*p);
+    e->rollout(env, *p);
     if (n_steps_out) *n_steps_out = e->roll_n;
     if (n_paths_out) *n_paths_out = e->roll_paths;
+  });
+}
+
+int trpo_rollout_cartpole(trpo_engine* e, const trpo_rollout_params* p, int64_t* n_steps_out, int64_t* n_paths_out) {
+  return trpo_rollout_env(e, TRPO_ENV_CARTPOLE_V0, p, n_steps_out, n_paths_out);
+}
+
+int trpo_rollout_fetch_states(trpo_engine* e, double* env_states, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
+    REQUIRE(env_states, "NULL argument");
+    e->use();
+    RolloutOut o{};
+    Staging st(mem, e->stream);
+    o.env_state = st.out(env_states, (size_t)e->roll_n * e->roll_args.state_dim);
+    e->rollout_compact(o);
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
   });
 }
 

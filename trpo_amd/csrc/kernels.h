@@ -759,7 +759,7 @@ void launch_adam(float* var, const float* g, float* m, float* v, int64_t n, floa
 
 namespace trpo {
 // ---------------------------------------------------------------------------
-// Batched sampling and CartPole-v0 rollouts (rollout.hip): agent.act
+// Batched sampling and rollouts of the built-in environments (rollout.hip): agent.act
 // (trpo_inksci.py:76-87), cat_sample (utils.py:95-105), rollout (utils.py:18-45)
 // ---------------------------------------------------------------------------
 struct PolicyShape {
@@ -767,7 +767,14 @@ struct PolicyShape {
   int w[kMaxLayers + 1];
   int64_t offW[kMaxLayers], offb[kMaxLayers];
 };
+struct EnvDims {            // one built-in environment (TRPO_ENV_*), from its trait in rollout.hip
+  int obs_dim, state_dim, n_actions, reset_draws, time_limit;
+  const char* name;
+};
+bool env_dims(int env, EnvDims* out);   // host-only; false for an unknown id
 struct RolloutArgs {
+  int env;                  // TRPO_ENV_*; ps must have its obs_dim and n_actions
+  int state_dim;            // the environment's
   PolicyShape ps;
   const float* theta;
   int maxw;                 // max layer width (LDS slice per wave: 2 * maxw floats)
@@ -776,10 +783,11 @@ struct RolloutArgs {
   int64_t env_cap;          // rows per environment region: budget + max episode length - 1
   int max_episodes;         // second dim of reset_u
   uint64_t seed;
-  const double* reset_u;    // optional [n_envs][max_episodes][4] uniforms for env.reset
+  const double* reset_u;    // optional [n_envs][max_episodes][reset_draws] uniforms for env.reset
   const double* act_u;      // optional [n_envs][env_cap] uniforms for cat_sample
   // per-environment regions (row = env * env_cap + i)
   double* obs;              // [.][obs_dim]
+  double* env_state;        // [.][state_dim] the state obs was made from; NULL where the observation is the state
   int64_t* actions;
   float* dist;              // [.][A]
   double* rewards;
@@ -789,13 +797,14 @@ struct RolloutArgs {
   int64_t* episodes;        // [n_envs] episodes collected
   // per-environment path regions (path = env * budget + episode; an environment starts at most budget episodes)
   uint8_t* end_truncated;   // 1: the path was cut off (time limit / max_pathlength), 0: the environment terminated
-  double* end_obs;          // [.][obs_dim] s_T, the state after the path's last step
+  double* end_obs;          // [.][obs_dim] the observation of s_T, the state after the path's last step
   float* end_dist;          // [.][A] the policy's distribution at s_T of a cut-off path, zeros otherwise
   int64_t* end_len;         // T, the path's step count
   int64_t* end_row;         // the path's last row within its environment's step region
 };
 struct RolloutOut {         // concatenated outputs; any pointer may be NULL
   double* obs64;            // [N][obs_dim]
+  double* env_state;        // [N][state_dim]
   float* X;                 // [N][ldx]   (engine batch: f32 states)
   int ldx;
   float* dist;              // [N][A]
@@ -826,4 +835,7 @@ void launch_act(const PolicyShape& ps, const float* theta, int maxw, const float
 void launch_cat_sample(const float* prob, int64_t n, int k, const double* r, int64_t* out, hipStream_t s);
 void launch_cartpole_step(const double* state, const int64_t* action, int64_t n, double* state_out, double* reward,
                           uint8_t* done, hipStream_t s);
+// state [n][state_dim] -> state_out, obs_out [n][obs_dim], reward, done (termination); outputs may be NULL
+void launch_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out,
+                     double* obs_out, double* reward, uint8_t* done, hipStream_t s);
 }  // namespace trpo

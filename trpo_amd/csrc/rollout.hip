@@ -1,4 +1,4 @@
-// Batched policy sampling and CartPole-v0 rollouts on the GPU (gfx950).
+// Batched policy sampling and rollouts of the built-in environments on the GPU (gfx950).
 //
 // Restates, data-parallel over environments:
 //   * agent.act (trpo_inksci.py:76-87): the policy forward on one state, then
@@ -13,6 +13,10 @@
 //     done past |x| > 2.4 or |theta| > 12 degrees, reward 1 per step, and the
 //     v0 TimeLimit of 200 steps.  gym is not vendored in the reference; this is
 //     its published classic_control/cartpole.py restated in float64 (Python floats).
+//   * MountainCar-v0 and Acrobot-v1, which the reference does not run: gym's classic_control tasks
+//     restated the same way (include/trpo_engine.h spells out their equations).  The rollout is one
+//     kernel over an environment trait (reset, step, observe and the dimensions), so that a task whose
+//     state is not its observation (Acrobot) or whose reward is not constant costs no second kernel.
 //
 // One wave simulates one environment for its whole share of the rollout: the
 // policy forward is wave-parallel over output units (activations in a per-wave
@@ -38,6 +42,7 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <stdexcept>
 
 #pragma clang fp contract(off)
 
@@ -94,6 +99,132 @@ __device__ __forceinline__ bool cartpole_step(double (&s)[4], int action) {
   s[2] = theta + kTau * theta_dot;
   s[3] = theta_dot + kTau * thetaacc;
   return s[0] < -kXThreshold || s[0] > kXThreshold || s[2] < -kThetaThreshold || s[2] > kThetaThreshold;
+}
+
+// The rollout's view of an environment.  kObsIsState: the observation is the state itself, so the per-step
+// record of the state is the record of the observation and no second array is written.
+struct CartPoleV0 {
+  static constexpr int kState = 4, kObs = 4, kActions = 2, kResetDraws = 4, kTimeLimit = 200;
+  static constexpr bool kObsIsState = true;
+  static constexpr const char* kName = "CartPole-v0";
+  // env.reset(): np_random.uniform(-0.05, 0.05, size=(4,))
+  static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = -0.05 + (0.05 - -0.05) * u[i];
+  }
+  static __device__ __forceinline__ bool step(double (&s)[kState], int action, double& reward) {
+    reward = 1.0;
+    return cartpole_step(s, action);
+  }
+  static __device__ __forceinline__ double observe(const double (&s)[kState], int i) { return s[i]; }
+};
+
+__device__ __forceinline__ double clampd(double x, double lo, double hi) {   // min(max(x, lo), hi)
+  const double a = lo > x ? lo : x;
+  return hi < a ? hi : a;
+}
+
+// ---- MountainCar-v0 (gym classic_control/mountain_car.py), float64 -----------------------------------
+struct MountainCarV0 {
+  static constexpr int kState = 2, kObs = 2, kActions = 3, kResetDraws = 1, kTimeLimit = 200;
+  static constexpr bool kObsIsState = true;
+  static constexpr const char* kName = "MountainCar-v0";
+  static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
+    s[0] = -0.6 + (-0.4 - -0.6) * u[0];
+    s[1] = 0.0;
+  }
+  static __device__ __forceinline__ bool step(double (&s)[kState], int action, double& reward) {
+    double p = s[0], v = s[1];
+    v = v + (double)(action - 1) * 0.001 + cos(3.0 * p) * (-0.0025);
+    v = clampd(v, -0.07, 0.07);
+    p = p + v;
+    p = clampd(p, -1.2, 0.6);
+    if (p == -1.2 && v < 0.0) v = 0.0;
+    s[0] = p;
+    s[1] = v;
+    reward = -1.0;
+    return p >= 0.5 && v >= 0.0;
+  }
+  static __device__ __forceinline__ double observe(const double (&s)[kState], int i) { return s[i]; }
+};
+
+// ---- Acrobot-v1 (gym classic_control/acrobot.py, "book" dynamics, one RK4 step), float64 -------------
+struct AcrobotV1 {
+  static constexpr int kState = 4, kObs = 6, kActions = 3, kResetDraws = 4, kTimeLimit = 500;
+  static constexpr bool kObsIsState = false;
+  static constexpr const char* kName = "Acrobot-v1";
+  static constexpr double kPi = 3.141592653589793;
+  static constexpr double m1 = 1.0, m2 = 1.0, l1 = 1.0, lc1 = 0.5, lc2 = 0.5, I1 = 1.0, I2 = 1.0, g = 9.8, dt = 0.2;
+  static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = -0.1 + (0.1 - -0.1) * u[i];
+  }
+  // d/dt (t1, t2, w1, w2) under torque a
+  static __device__ __forceinline__ void deriv(const double (&y)[4], double a, double (&k)[4]) {
+    const double t1 = y[0], t2 = y[1], w1 = y[2], w2 = y[3];
+    const double c2 = cos(t2), s2 = sin(t2);
+    const double d1 = m1 * (lc1 * lc1) + m2 * (l1 * l1 + lc2 * lc2 + 2 * l1 * lc2 * c2) + I1 + I2;
+    const double d2 = m2 * (lc2 * lc2 + l1 * lc2 * c2) + I2;
+    const double phi2 = m2 * lc2 * g * cos(t1 + t2 - kPi / 2);
+    const double phi1 = -m2 * l1 * lc2 * (w2 * w2) * s2 - 2 * m2 * l1 * lc2 * w2 * w1 * s2 +
+                        (m1 * lc1 + m2 * l1) * g * cos(t1 - kPi / 2) + phi2;
+    const double dd2 =
+        (a + d2 / d1 * phi1 - m2 * l1 * lc2 * (w1 * w1) * s2 - phi2) / (m2 * (lc2 * lc2) + I2 - (d2 * d2) / d1);
+    const double dd1 = -(d2 * dd2 + phi1) / d1;
+    k[0] = w1;
+    k[1] = w2;
+    k[2] = dd1;
+    k[3] = dd2;
+  }
+  // while x > pi: x -= 2 pi; while x < -pi: x += 2 pi.  From a state in range one step moves an angle by a few
+  // turns at most; an angle that is not finite or absurdly large (only trpo_env_step can be handed one) is
+  // left as it is rather than looped on.
+  static __device__ __forceinline__ double wrap(double x) {
+    if (!(fabs(x) < 1e5)) return x;
+    while (x > kPi) x -= 2 * kPi;
+    while (x < -kPi) x += 2 * kPi;
+    return x;
+  }
+  static __device__ __forceinline__ bool step(double (&s)[kState], int action, double& reward) {
+    const double a = (double)(action - 1);
+    double k1[4], k2[4], k3[4], k4[4], y[4];
+    deriv(s, a, k1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = s[i] + dt / 2 * k1[i];
+    deriv(y, a, k2);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = s[i] + dt / 2 * k2[i];
+    deriv(y, a, k3);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = s[i] + dt * k3[i];
+    deriv(y, a, k4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = s[i] + dt / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+    s[0] = wrap(s[0]);
+    s[1] = wrap(s[1]);
+    s[2] = clampd(s[2], -4 * kPi, 4 * kPi);
+    s[3] = clampd(s[3], -9 * kPi, 9 * kPi);
+    const bool done = -cos(s[0]) - cos(s[1] + s[0]) > 1.0;
+    reward = done ? 0.0 : -1.0;
+    return done;
+  }
+  // (cos t1, sin t1, cos t2, sin t2, w1, w2)
+  static __device__ __forceinline__ double observe(const double (&s)[kState], int i) {
+    if (i >= 4) return i == 4 ? s[2] : s[3];
+    const double th = i < 2 ? s[0] : s[1];
+    return (i & 1) ? sin(th) : cos(th);
+  }
+};
+
+// env id (TRPO_ENV_*) -> trait; false for an unknown id
+template <class F>
+bool with_env(int env, F&& f) {
+  switch (env) {
+    case 0: f(CartPoleV0{}); return true;
+    case 1: f(MountainCarV0{}); return true;
+    case 2: f(AcrobotV1{}); return true;
+    default: return false;
+  }
 }
 
 // ---- wave-level policy forward ---------------------------------------------------------------
@@ -169,27 +300,28 @@ __device__ __forceinline__ int wave_choose(float p, int A, double r, int train, 
 
 constexpr int kRollWaves = 4;
 
+template <class Env>
 __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutArgs a) {
   extern __shared__ float lds[];
+  constexpr int kS = Env::kState, obs_dim = Env::kObs, A = Env::kActions;   // the engine checked ps against them
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int env = blockIdx.x * kRollWaves + wv;
   if (env >= a.n_envs) return;
   float* buf0 = lds + (size_t)wv * 2 * a.maxw;
   float* buf1 = buf0 + a.maxw;
-  const int obs_dim = a.ps.w[0], A = a.ps.w[a.ps.L];
   const int64_t base = (int64_t)env * a.env_cap;
   int64_t count = 0;
   int episode = 0;
   uint64_t adraw = 0;
   while (count < a.budget) {
-    // env.reset(): np_random.uniform(-0.05, 0.05, size=(4,))
-    double s[4];
+    // env.reset() from kResetDraws uniforms
+    double u[Env::kResetDraws];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const double u = a.reset_u ? a.reset_u[((int64_t)env * a.max_episodes + episode) * 4 + i]
-                                 : uniform53(a.seed, (uint32_t)env, 1u, (uint64_t)episode * 4 + i);
-      s[i] = -0.05 + (0.05 - -0.05) * u;
-    }
+    for (int i = 0; i < Env::kResetDraws; ++i)
+      u[i] = a.reset_u ? a.reset_u[((int64_t)env * a.max_episodes + episode) * Env::kResetDraws + i]
+                       : uniform53(a.seed, (uint32_t)env, 1u, (uint64_t)episode * Env::kResetDraws + i);
+    double s[kS];
+    Env::reset(s, u);
     ++episode;
     bool done = false;
     int len = 0;
@@ -197,8 +329,12 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
       const int64_t row = base + count;
       // act(ob): the obs fed to the float32 state placeholder, recorded as the float64 ob
       if (lane < obs_dim) {
-        buf0[lane] = (float)s[lane];
-        a.obs[row * obs_dim + lane] = s[lane];
+        const double ob = Env::observe(s, lane);
+        buf0[lane] = (float)ob;
+        a.obs[row * obs_dim + lane] = ob;
+      }
+      if constexpr (!Env::kObsIsState) {
+        if (lane < kS) a.env_state[row * kS + lane] = s[lane];
       }
       wave_sync();
       const float p = wave_policy(a.ps, a.theta, buf0, buf1, lane);
@@ -206,34 +342,36 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
       ++adraw;
       const int action = wave_choose(p, A, r, a.train, lane);
       if (lane < A) a.dist[row * A + lane] = p;
-      done = cartpole_step(s, action);
+      double reward;
+      done = Env::step(s, action, reward);
       if (lane == 0) {
         a.actions[row] = action;
-        a.rewards[row] = 1.0;
+        a.rewards[row] = reward;
         a.starts[row] = t == 0 ? 1 : 0;
         if (a.uniforms_out) a.uniforms_out[row] = r;
       }
       ++count;
       len = t + 1;
-      // CartPole-v0's TimeLimit(max_episode_steps=200) reports done at step 200
+      // the TimeLimit wrapper (CartPole-v0: max_episode_steps=200) reports done at its last step
       if (done || t + 1 >= a.time_limit) break;
       wave_sync();
     }
     wave_sync();
     // How the path ended.  It was cut off (truncated) when its last step did not terminate the environment:
     // the time limit or max_pathlength ended it, and a step that does both counts as terminated.  s is s_T;
-    // a cut-off path also records the policy's distribution there, the VF's features of s_T (vf.hip).  The
-    // extra forward draws no uniform.
+    // its observation is recorded, and a cut-off path also records the policy's distribution there, the VF's
+    // features of s_T (vf.hip).  The extra forward draws no uniform.
     const int64_t path = (int64_t)env * a.budget + (episode - 1);
     const bool truncated = !done;
+    const double obT = lane < obs_dim ? Env::observe(s, lane) : 0.0;
     float pT = 0.0f;
     if (truncated) {
-      if (lane < obs_dim) buf0[lane] = (float)s[lane];
+      if (lane < obs_dim) buf0[lane] = (float)obT;
       wave_sync();
       pT = wave_policy(a.ps, a.theta, buf0, buf1, lane);
       wave_sync();
     }
-    if (lane < obs_dim) a.end_obs[path * obs_dim + lane] = s[lane];
+    if (lane < obs_dim) a.end_obs[path * obs_dim + lane] = obT;
     if (lane < A) a.end_dist[path * A + lane] = pT;
     if (lane == 0) {
       a.end_truncated[path] = truncated ? 1 : 0;
@@ -270,6 +408,10 @@ __global__ void __launch_bounds__(256) rollout_compact_kernel(const RolloutArgs 
     if (o.rewards) o.rewards[d] = a.rewards[s];
     if (o.starts) o.starts[d] = a.starts[s];
     if (o.uniforms && a.uniforms_out) o.uniforms[d] = a.uniforms_out[s];
+    if (o.env_state) {   // an environment whose observation is its state recorded it once, as obs
+      const double* st = a.env_state ? a.env_state : a.obs;
+      for (int c = 0; c < a.state_dim; ++c) o.env_state[d * a.state_dim + c] = st[s * a.state_dim + c];
+    }
   }
   // the per-path end records; path offsets = exclusive sums of the environments' episode counts
   if (!o.path_offsets) return;
@@ -336,6 +478,31 @@ __global__ void __launch_bounds__(256) cartpole_step_kernel(const double* state,
   }
 }
 
+// one step per row of any environment: the state after it, its observation, reward and termination
+template <class Env>
+__global__ void __launch_bounds__(256) env_step_kernel(const double* state, const int64_t* action, int64_t n,
+                                                       double* state_out, double* obs_out, double* reward,
+                                                       uint8_t* done) {
+  constexpr int kS = Env::kState, kO = Env::kObs;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    double s[kS];
+#pragma unroll
+    for (int j = 0; j < kS; ++j) s[j] = state[kS * i + j];
+    double rw;
+    const bool d = Env::step(s, (int)action[i], rw);
+    if (state_out) {
+#pragma unroll
+      for (int j = 0; j < kS; ++j) state_out[kS * i + j] = s[j];
+    }
+    if (obs_out) {
+#pragma unroll
+      for (int j = 0; j < kO; ++j) obs_out[kO * i + j] = Env::observe(s, j);
+    }
+    if (reward) reward[i] = rw;
+    if (done) done[i] = d ? 1 : 0;
+  }
+}
+
 inline unsigned grid1(int64_t n) {
   const int64_t b = (n + 255) / 256;
   return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -345,9 +512,20 @@ inline unsigned grid1(int64_t n) {
 
 size_t rollout_lds_bytes(int maxw) { return (size_t)kRollWaves * 2 * maxw * sizeof(float); }
 
+bool env_dims(int env, EnvDims* out) {
+  return with_env(env, [&](auto e) {
+    using Env = decltype(e);
+    *out = EnvDims{Env::kObs, Env::kState, Env::kActions, Env::kResetDraws, Env::kTimeLimit, Env::kName};
+  });
+}
+
 void launch_rollout(const RolloutArgs& a, hipStream_t s) {
   const unsigned blocks = (unsigned)((a.n_envs + kRollWaves - 1) / kRollWaves);
-  hipLaunchKernelGGL(rollout_kernel, dim3(blocks), dim3(kRollWaves * 64), rollout_lds_bytes(a.maxw), s, a);
+  const bool known = with_env(a.env, [&](auto e) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rollout_kernel<decltype(e)>), dim3(blocks), dim3(kRollWaves * 64),
+                       rollout_lds_bytes(a.maxw), s, a);
+  });
+  if (!known) throw std::invalid_argument("launch_rollout: unknown environment id");
 }
 
 void launch_rollout_compact(const RolloutArgs& a, const int64_t* offsets, const RolloutOut& o, int64_t max_count,
@@ -372,6 +550,16 @@ void launch_cartpole_step(const double* state, const int64_t* action, int64_t n,
                           uint8_t* done, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(cartpole_step_kernel, dim3(grid1(n)), dim3(256), 0, s, state, action, n, state_out, reward, done);
+}
+
+void launch_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out,
+                     double* obs_out, double* reward, uint8_t* done, hipStream_t s) {
+  const bool known = with_env(env, [&](auto e) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(env_step_kernel<decltype(e)>), dim3(grid1(n)), dim3(256), 0, s, state, action,
+                       n, state_out, obs_out, reward, done);
+  });
+  if (!known) throw std::invalid_argument("launch_env_step: unknown environment id");
 }
 
 }  // namespace trpo

@@ -37,6 +37,51 @@ void trpo_default_rollout_params(trpo_rollout_params* p) {
   p->mem = TRPO_MEM_HOST;
 }
 
+int trpo_env_info(int env, trpo_env_info_t* out) {
+  return guarded([&] {
+    REQUIRE(out, "NULL argument");
+    EnvDims d{};
+    REQUIRE(env_dims(env, &d), "unknown environment id " + std::to_string(env));
+    std::memset(out, 0, sizeof *out);
+    out->obs_dim = d.obs_dim;
+    out->state_dim = d.state_dim;
+    out->n_actions = d.n_actions;
+    out->reset_draws = d.reset_draws;
+    out->time_limit = d.time_limit;
+    std::strncpy(out->name, d.name, sizeof out->name - 1);
+  });
+}
+
+int trpo_default_rollout_params_env(int env, trpo_rollout_params* p) {
+  return guarded([&] {
+    REQUIRE(p, "NULL argument");
+    EnvDims d{};
+    REQUIRE(env_dims(env, &d), "unknown environment id " + std::to_string(env));
+    trpo_default_rollout_params(p);
+    p->time_limit = d.time_limit;
+  });
+}
+
+int trpo_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out, double* obs_out,
+                  double* reward, uint8_t* done, int mem) {
+  return guarded([&] {
+    EnvDims d{};
+    REQUIRE(env_dims(env, &d), "unknown environment id " + std::to_string(env));
+    REQUIRE(state && action && n >= 0, "bad argument");
+    if (n == 0) return;
+    Staging st(mem, nullptr);
+    const double* ds = st.in(state, (size_t)n * d.state_dim);
+    const int64_t* da = st.in(action, (size_t)n);
+    double* dso = st.out(state_out, (size_t)n * d.state_dim);
+    double* dob = st.out(obs_out, (size_t)n * d.obs_dim);
+    double* dr = st.out(reward, (size_t)n);
+    launch_env_step(env, ds, da, n, dso, dob, dr, st.out(done, (size_t)n), nullptr);
+    check_launch();
+    st.fetch();
+    HIPCHECK(hipDeviceSynchronize());
+  });
+}
+
 int trpo_device_count(int* out) {
   return guarded([&] {
     REQUIRE(out, "NULL argument");

@@ -16,9 +16,30 @@ import numpy as np
 from . import _lib
 from ._lib import MEM_DEVICE, MEM_HOST, check, lib
 
-__all__ = ["Engine", "UpdateParams"]
+__all__ = ["Engine", "UpdateParams", "ENVS", "env_info", "env_step_device"]
 
 _ADV_KINDS = {"returns": _lib.ADV_RETURNS, "gae": _lib.ADV_GAE}
+
+# the built-in environments of rollout.hip: name -> TRPO_ENV_* id
+ENVS = {"CartPole-v0": _lib.ENV_CARTPOLE_V0, "MountainCar-v0": _lib.ENV_MOUNTAINCAR_V0,
+        "Acrobot-v1": _lib.ENV_ACROBOT_V1}
+
+
+def _env_id(env) -> int:
+    if isinstance(env, str):
+        if env not in ENVS:
+            raise ValueError(f"unknown environment {env!r}; built in: {sorted(ENVS)}")
+        return ENVS[env]
+    return int(env)
+
+
+def env_info(env) -> dict:
+    """The table of a built-in environment (a name of ENVS or a TRPO_ENV_* id): obs_dim, state_dim, n_actions,
+    reset_draws, time_limit, name.  Host-only: needs no GPU."""
+    info = _lib.EnvInfo()
+    check(lib.trpo_env_info(_env_id(env), ctypes.byref(info)), "trpo_env_info")
+    return {"obs_dim": info.obs_dim, "state_dim": info.state_dim, "n_actions": info.n_actions,
+            "reset_draws": info.reset_draws, "time_limit": info.time_limit, "name": info.name.decode()}
 
 
 def _is_torch(x) -> bool:
@@ -353,6 +374,24 @@ class Engine:
         instances on the GPU.  Returns (total steps, number of paths)."""
         p = _lib.RolloutParams()
         lib.trpo_default_rollout_params(ctypes.byref(p))
+        return self._rollout(None, p, n_envs, n_timesteps, max_pathlength, seed, train, time_limit,
+                             reset_uniforms, action_uniforms, max_episodes_per_env)
+
+    def rollout(self, env="CartPole-v0", n_envs: int = 1, n_timesteps: int = 1000, max_pathlength: int = 1000,
+                seed: int = 1, train: bool = True, time_limit: Optional[int] = None,
+                reset_uniforms=None, action_uniforms=None, max_episodes_per_env: int = 0):
+        """rollout_cartpole for any built-in environment (a name of ENVS): the engine's obs_dim and n_actions
+        must be the environment's.  time_limit=None is the environment's own; injected reset_uniforms are
+        [n_envs, max_episodes_per_env, reset_draws].  Returns (total steps, number of paths)."""
+        eid = _env_id(env)
+        p = _lib.RolloutParams()
+        check(lib.trpo_default_rollout_params_env(eid, ctypes.byref(p)), "trpo_default_rollout_params_env")
+        return self._rollout(eid, p, n_envs, n_timesteps, max_pathlength, seed, train,
+                             p.time_limit if time_limit is None else time_limit,
+                             reset_uniforms, action_uniforms, max_episodes_per_env)
+
+    def _rollout(self, eid, p, n_envs, n_timesteps, max_pathlength, seed, train, time_limit,
+                 reset_uniforms, action_uniforms, max_episodes_per_env):
         p.n_envs, p.n_timesteps, p.max_pathlength = int(n_envs), int(n_timesteps), int(max_pathlength)
         p.seed, p.train, p.time_limit = int(seed) & ((1 << 64) - 1), int(bool(train)), int(time_limit)
         keep = []
@@ -369,15 +408,32 @@ class Engine:
             p.mem = au.mem
         n = ctypes.c_int64(0)
         paths = ctypes.c_int64(0)
-        check(lib.trpo_rollout_cartpole(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
-              "trpo_rollout_cartpole")
+        if eid is None:
+            check(lib.trpo_rollout_cartpole(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
+                  "trpo_rollout_cartpole")
+            eid = _lib.ENV_CARTPOLE_V0
+        else:
+            check(lib.trpo_rollout_env(self._h, eid, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
+                  "trpo_rollout_env")
         self.rollout_steps = n.value
         self.rollout_paths = paths.value
+        self.rollout_state_dim = env_info(eid)["state_dim"]
         self._tail_ptr = None
         return n.value, paths.value
 
+    def rollout_fetch_states(self) -> np.ndarray:
+        """The environment state every observation of the last rollout was made from, f64 [N, state_dim] (host);
+        for CartPole-v0 and MountainCar-v0 it equals obs."""
+        if getattr(self, "rollout_steps", None) is None:
+            # no rollout yet: the engine reports the state error
+            check(lib.trpo_rollout_fetch_states(self._h, None, MEM_HOST), "trpo_rollout_fetch_states")
+        out = np.empty((self.rollout_steps, self.rollout_state_dim))
+        check(lib.trpo_rollout_fetch_states(self._h, out.ctypes.data_as(ctypes.c_void_p), MEM_HOST),
+              "trpo_rollout_fetch_states")
+        return out
+
     def rollout_fetch(self, device=None):
-        """The concatenated rollout as the reference's arrays: obs f64 [N,4] (and f32), actions i64,
+        """The concatenated rollout as the reference's arrays: obs f64 [N,obs_dim] (and f32), actions i64,
         action_dists f32 [N,A], rewards f64, episode starts u8, cat_sample uniforms f64 (numpy, or torch
         tensors on `device` -- torch must have initialised its GPU context before the first engine was
         created: it bundles its own HIP runtime, which cannot start after ours)."""
@@ -415,7 +471,7 @@ class Engine:
     def rollout_fetch_ends(self):
         """How each path of the last rollout ended, in the order of the concatenated rollout (host arrays):
         truncated u8 [P] (1 = cut off by the time limit or max_pathlength, 0 = the environment terminated),
-        final_obs f64 [P,4] (s_T, the state after the last step), final_dists f32 [P,A] (the policy at
+        final_obs f64 [P,obs_dim] (the observation of s_T, the state after the last step), final_dists f32 [P,A] (the policy at
         float32(s_T) for cut-off paths, zeros otherwise), lengths i64 [P] and end_rows i64 [P] (the row of
         each path's last step)."""
         if getattr(self, "rollout_paths", None) is None:
@@ -500,6 +556,23 @@ def cartpole_step_device(state, action):
                                  so.ctypes.data_as(ctypes.c_void_p), rw.ctypes.data_as(ctypes.c_void_p),
                                  dn.ctypes.data_as(ctypes.c_void_p), MEM_HOST), "trpo_cartpole_step")
     return so, rw, dn.astype(bool)
+
+
+def env_step_device(env, state, action):
+    """One step per row of a built-in environment on the current GPU: (state_out [n, state_dim], obs
+    [n, obs_dim] of state_out, reward [n], done [n] bool; done is termination, not the time limit)."""
+    eid = _env_id(env)
+    info = env_info(eid)
+    s = np.ascontiguousarray(state, np.float64).reshape(-1, info["state_dim"])
+    a = np.ascontiguousarray(action, np.int64).reshape(-1)
+    n = s.shape[0]
+    if a.shape[0] != n:
+        raise ValueError(f"{n} states but {a.shape[0]} actions")
+    so, ob = np.empty((n, info["state_dim"])), np.empty((n, info["obs_dim"]))
+    rw, dn = np.empty(n), np.empty(n, np.uint8)
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    check(lib.trpo_env_step(eid, ptr(s), ptr(a), n, ptr(so), ptr(ob), ptr(rw), ptr(dn), MEM_HOST), "trpo_env_step")
+    return so, ob, rw, dn.astype(bool)
 
 
 def discount_device(x, gamma: float, episode_starts=None) -> np.ndarray:
