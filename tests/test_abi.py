@@ -95,3 +95,35 @@ def test_every_documented_option_is_known():
     assert get_option("hbwd2") == 2 and get_option("head_fwd") == 1 and get_option("ls_fused") == 1
     assert get_option("cg_fuse_reduce") == 1 and get_option("rfwd01") == 1 and get_option("cg_p_img") == 1
     assert get_option("fwd01") == 1
+
+
+OPTION_DEFAULTS = {
+    "split_mfma": 5, "split_wg": 1, "chain": 1, "split_f16": 1, "split_min_k": 0, "graphs": 1, "tail": 1,
+    "fused": 3, "low_seg": 14, "planes": 1, "rbwd0": 1, "hbwd2": 2, "head_fwd": 1, "splits": 0, "pg_splits": 0,
+    "ls_fused": 1, "cg_fuse_reduce": 1, "cg_p_img": 1, "rfwd01": 1, "fwd01": 1, "rh1_planes": 1,
+}
+
+
+def _options_in_child(names, extra_env):
+    """get_option of `names` in a fresh process whose environment holds no TRPO_<OPTION> variable but `extra_env`."""
+    import json
+    import sys
+    env = {k: v for k, v in os.environ.items() if k[5:].lower() not in OPTION_DEFAULTS or not k.startswith("TRPO_")}
+    env.update(extra_env)
+    code = ("import json, sys; from trpo_amd._lib import get_option; "
+            "print(json.dumps({n: get_option(n) for n in sys.argv[1:]}))")
+    out = subprocess.run([sys.executable, "-c", code, *names], env=env, cwd=ROOT, capture_output=True, text=True,
+                         check=True)
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_option_defaults_without_environment():
+    """With no TRPO_<OPTION> variable set, every option reads its documented default."""
+    assert len(OPTION_DEFAULTS) == 21
+    assert _options_in_child(sorted(OPTION_DEFAULTS), {}) == OPTION_DEFAULTS
+
+
+def test_options_read_the_environment():
+    """An option's environment variable overrides its default at load; the others keep theirs."""
+    got = _options_in_child(["low_seg", "fused", "tail"], {"TRPO_LOW_SEG": "9", "TRPO_FUSED": "2"})
+    assert got == {"low_seg": 9, "fused": 2, "tail": 1}

@@ -1,6 +1,6 @@
 // Standalone timing harness for the row/weight-gradient GEMMs (not part of the product).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Itrpo_amd/csrc tools/gemm_bench.cpp \
-//        trpo_amd/csrc/gemm.hip -o tools/gemm_bench
+//        trpo_amd/csrc/gemm.hip trpo_amd/csrc/options.cpp -o tools/gemm_bench
 // run:   tools/gemm_bench [M] [reps]
 // Operands are random (zero data lets the clock run high and overstates throughput).
 #include <hip/hip_runtime.h>

@@ -2,7 +2,7 @@
 // (gemm.hip rowgemm3, config 5) on the C4 FVP shapes (not part of the product).
 // build (after `make -C trpo_amd/csrc`):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Itrpo_amd/csrc tools/plane_bench.cpp \
-//     build/csrc/gemm.hip.o build/csrc/plane.hip.o build/csrc/vec.hip.o -o tools/plane_bench
+//     build/csrc/gemm.hip.o build/csrc/plane.hip.o build/csrc/vec.hip.o build/csrc/options.cpp.o -o tools/plane_bench
 // run: tools/plane_bench [M] [reps]
 #include <hip/hip_runtime.h>
 #include <cmath>

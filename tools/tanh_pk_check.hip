@@ -1,10 +1,10 @@
-// Standalone check of rowepi.h tanh_fast against a packed-f32 form of the same arithmetic (two values per
+// Standalone check of split.h tanh_fast against a packed-f32 form of the same arithmetic (two values per
 // v_pk_fma_f32 / v_pk_mul_f32): max |difference| over a sweep of inputs.  hipcc --offload-arch=gfx950 -O3
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
 #include <vector>
-#include "rowepi.h"
+#include "split.h"
 
 using trpo::tanh_fast;
 typedef float tf2 __attribute__((ext_vector_type(2)));

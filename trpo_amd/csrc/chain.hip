@@ -23,8 +23,8 @@
 //    trip.  The k order this implies (chain_perm) is absorbed into the weight
 //    images.
 //  * fp32 accuracy on bf16 MFMA: both operands are split exactly into
-//    hi + mid + lo bf16 pieces and 6 products are accumulated in f32 (the same
-//    scheme as gemm.hip's split path).
+//    hi + mid + lo bf16 pieces and 6 products are accumulated in f32 (split.h
+//    split3 / mfma6).
 //  * Weights stream through LDS in 32-deep k-chunks shared by all waves of the
 //    workgroup, from pre-split, pre-permuted, pre-swizzled images (built by
 //    chain_img_kernel: theta parts once per prepare, tangent parts per FVP), so
@@ -61,23 +61,23 @@ __global__ void __launch_bounds__(256) chain_img_kernel(const ChainImgArgs a, co
   const int o = (idx >> 2) % j.otp;
   const int c = (idx >> 2) / j.otp;
   const float* src = (which ? v : theta) + j.src_off;
-  cu16x8 h, m, l;
+  u16x8 h, m, l;
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int k = 32 * c + chain_perm(8 * gg + q);
     float x = 0.0f;
     if (o < j.O && k < j.K) x = j.trans ? src[(size_t)o * j.ldw + k] : src[(size_t)k * j.ldw + o];
     unsigned short hh, mm, ll;
-    csplit(x, hh, mm, ll);
+    split3(x, hh, mm, ll);
     h[q] = hh;
     m[q] = mm;
     l[q] = ll;
   }
   unsigned short* dst = a.img + j.dst_off + (size_t)c * 3 * j.otp * 32 + o * 32 + ((gg ^ chain_hsw(o)) << 3);
   const size_t pl = (size_t)j.otp * 32;
-  *reinterpret_cast<cu16x8*>(dst) = h;
-  *reinterpret_cast<cu16x8*>(dst + pl) = m;
-  *reinterpret_cast<cu16x8*>(dst + 2 * pl) = l;
+  *reinterpret_cast<u16x8*>(dst) = h;
+  *reinterpret_cast<u16x8*>(dst + pl) = m;
+  *reinterpret_cast<u16x8*>(dst + 2 * pl) = l;
 }
 
 // ---------------------------------------------------------------------------
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
   constexpr int CHU = 12 * 16 * OTM;   // 16-B units of the largest chunk: 3 planes x 16*OTM rows x 64 B
   constexpr int NLD = (CHU + NT - 1) / NT;
   constexpr int RB = 16 * WAVES;       // states per workgroup
-  __shared__ cu32x4 wl[CHU];
+  __shared__ u32x4 wl[CHU];
   if (a.skip && *a.skip) return;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, vo, 0, 0));
   };
   auto st4 = [&](f32x4 x, __amdgpu_buffer_rsrc_t r, int vo) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cu32x4, x), r, vo, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), r, vo, 0, 0);
   };
   // tangent bias c_l at this lane's features of tile t
   auto bias4 = [&](int l, int t) -> f32x4 {
@@ -136,13 +136,11 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
         __builtin_amdgcn_make_buffer_rsrc((void*)(a.v + a.offb[l]), 0, a.w[l + 1] * 4, 0x00020000);
     const int o = (16 * t + 4 * g) * 4;
     f32x4 r;
-    r[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, o, 0, 0));
-    r[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, o + 4, 0, 0));
-    r[2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, o + 8, 0, 0));
-    r[3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, o + 12, 0, 0));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = ldbuf(rc, o + 4 * i, 0);
     return r;
   };
-  auto mkb = [&](const f32x4& x0, const f32x4& x1, cbf16x8 (&b)[3]) { chain_mkb(x0, x1, b); };
+  auto mkb = [&](const f32x4& x0, const f32x4& x1, bf16x8 (&b)[3]) { chain_mkb(x0, x1, b); };
 
   f32x4 acc[OTM], S[OTM], PF[OTM];   // S: first-segment source (RH_l / RD_l); PF: prefetched epilogue operand
 #pragma unroll
@@ -161,15 +159,15 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
   };
 
   // ---- weight-chunk stream (consumption order = a.tab) ----
-  const cu32x4* img = reinterpret_cast<const cu32x4*>(a.img);
-  cu32x4 wr[NLD];
+  const u32x4* img = reinterpret_cast<const u32x4*>(a.img);
+  u32x4 wr[NLD];
   int q = 0;
   // branch-free (no exec-masked loads or stores, so vmcnt waits stay counted): past the
   // last chunk the last one is re-read; lanes past a small chunk re-read its last unit
   auto gload = [&](int qq) {
     qq = qq < a.nchunks ? qq : a.nchunks - 1;
     const int off = a.tab[2 * qq], sz = a.tab[2 * qq + 1];
-    const cu32x4* src = img + off;
+    const u32x4* src = img + off;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = tid + i * NT;
@@ -196,41 +194,26 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
   // acc[0..OT) += W^T * B over the chunk in LDS.  The tile loop is branch-free
   // for the compile-time counts (all OTM tiles, or a head's 1-2) where registers
   // allow, so the LDS reads of a tile are issued under the MFMAs of the previous.
-  auto mma_tile = [&](const unsigned short* W, int pl, int ot, const cbf16x8 (&b)[3]) __attribute__((always_inline)) {
-    const cbf16x8 a0 = *reinterpret_cast<const cbf16x8*>(W + ot * 512);
-    const cbf16x8 a1 = *reinterpret_cast<const cbf16x8*>(W + pl + ot * 512);
-    const cbf16x8 a2 = *reinterpret_cast<const cbf16x8*>(W + 2 * pl + ot * 512);
-    f32x4 c = acc[ot];
-    // smallest terms first
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[0], c, 0, 0, 0);
-    acc[ot] = c;
+  auto mma_tile = [&](const unsigned short* W, int pl, int ot, const bf16x8 (&b)[3]) __attribute__((always_inline)) {
+    const bf16x8 w3[3] = {*reinterpret_cast<const bf16x8*>(W + ot * 512),
+                          *reinterpret_cast<const bf16x8*>(W + pl + ot * 512),
+                          *reinterpret_cast<const bf16x8*>(W + 2 * pl + ot * 512)};
+    acc[ot] = mfma6(w3, b, acc[ot]);
   };
-  auto mma = [&](int OT, const cbf16x8 (&b)[3]) __attribute__((always_inline)) {
+  auto mma = [&](int OT, const bf16x8 (&b)[3]) __attribute__((always_inline)) {
     const unsigned short* W = reinterpret_cast<const unsigned short*>(&wl[0]) + frag;
     const int pl = OT * 512;   // u16 per plane
     if ((PIPE || OTM < 16) && OT == OTM) {
-      cbf16x8 f[3], nx[3];
+      bf16x8 f[3], nx[3];
 #pragma unroll
-      for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const cbf16x8*>(W + p * pl);
+      for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const bf16x8*>(W + p * pl);
 #pragma unroll
       for (int ot = 0; ot < OTM; ++ot) {
         if (ot + 1 < OTM) {
 #pragma unroll
-          for (int p = 0; p < 3; ++p) nx[p] = *reinterpret_cast<const cbf16x8*>(W + p * pl + (ot + 1) * 512);
+          for (int p = 0; p < 3; ++p) nx[p] = *reinterpret_cast<const bf16x8*>(W + p * pl + (ot + 1) * 512);
         }
-        f32x4 c = acc[ot];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[2], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], b[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], b[0], c, 0, 0, 0);
-        acc[ot] = c;
+        acc[ot] = mfma6(f, b, acc[ot]);
         if (ot + 1 < OTM) {
 #pragma unroll
           for (int p = 0; p < 3; ++p) f[p] = nx[p];
@@ -271,7 +254,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
       m1 = mld(1, 1);
     }
     auto seg0_chunk = [&](int c, int kcc) __attribute__((always_inline)) {
-      cbf16x8 b[3];
+      bf16x8 b[3];
       mkb(S[2 * c], 2 * c + 1 < OTM ? S[2 * c + 1] : z4, b);
       chunk_begin();
       // the previous epilogue's stores (S is overwritten only by this step's epilogue;
@@ -319,7 +302,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
 #pragma unroll
         for (int t = 0; t < OTM; ++t) PF[t] = ld4(rp, t < OTp ? voff(ldp, t) : rb * ldp * 4);
       }
-      cbf16x8 b[3];
+      bf16x8 b[3];
       mkb(x0, x1, b);
       mma(OT, b);
     };
@@ -348,7 +331,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
         f32x4 r;
         const f32x4 h = pre(a.H[j], ldj, t);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = c_one_minus_sq(h[i]) * (acc[t][i] + cb[i]);
+        for (int i = 0; i < 4; ++i) r[i] = one_minus_sq(h[i]) * (acc[t][i] + cb[i]);
         S[t] = r;
       } else {
         S[t] = z4;
@@ -427,7 +410,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC) fvp_chain_kernel(const ChainA
         const f32x4 h = ld4(rH, vo), rh = ld4(rR, vo), e = pre(a.E[l - 1], ldl, t);
         f32x4 r;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = fmaf(e[i], rh[i], acc[t][i] * c_one_minus_sq(h[i]));
+        for (int i = 0; i < 4; ++i) r[i] = fmaf(e[i], rh[i], acc[t][i] * one_minus_sq(h[i]));
         S[t] = r;
       } else {
         S[t] = z4;

@@ -1,29 +1,10 @@
 // Device helpers shared by the fused FVP chain (chain.hip) and the fused small-width FVPs
-// (fused.hip, fused16.hip): the exact bf16 three-way split, the layout of the chain's weight images
-// and of the gradient-pass images.
+// (fused.hip, fused16.hip): the layout of the chain's weight images and of the gradient-pass images.
 #pragma once
-#include "common.h"
+#include "split.h"
 
 namespace trpo {
-
-typedef __bf16 cbf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short cu16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short cu16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
-typedef short fs4 __attribute__((ext_vector_type(4)));   // ds_read_b64_tr_b16 results
-typedef short fs8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned short cb_bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ float cb_val(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
-
-// x = hi + mid + lo exactly (each a bf16), as gemm.hip's split3
-__device__ __forceinline__ void csplit(float x, unsigned short& h, unsigned short& m, unsigned short& l) {
-  h = cb_bits(x);
-  const float r1 = x - cb_val(h);
-  m = cb_bits(r1);
-  const float r2 = r1 - cb_val(m);
-  l = cb_bits(r2);
-}
+namespace {
 
 // Gradient-pass images of the fused FVPs (fused.hip, fused16.hip): [state][kFI features] 16-bit planes.
 constexpr int kFI = 64;   // features per image row (one pass operand: up to 4 tiles of 16)
@@ -50,43 +31,30 @@ __host__ __device__ constexpr int chain_perm(int kk) {
   return (kk & 7) < 4 ? 4 * (kk >> 3) + (kk & 7) : 16 + 4 * (kk >> 3) + (kk & 7) - 4;
 }
 
-__device__ __forceinline__ float c_one_minus_sq(float h) { return (1.0f - h) * (1.0f + h); }
-
 __device__ __forceinline__ double sum4lanes(double v) {   // lanes s, s+16, s+32, s+48 (common.h swaps)
   return xadd_d<true>(xadd_d<false>(v));
 }
 
 // B operand (3 bf16 planes) of v_mfma_f32_16x16x32_bf16 from two acc-layout tiles: lane (g, s)
 // holds features 4g..4g+3 of each tile for state s (the k order chain_perm describes)
-__device__ __forceinline__ void chain_mkb(const f32x4& x0, const f32x4& x1, cbf16x8 (&b)[3]) {
-  cu16x8 h, m, l;
+__device__ __forceinline__ void chain_mkb(const f32x4& x0, const f32x4& x1, bf16x8 (&b)[3]) {
+  u16x8 h, m, l;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     unsigned short hh, mm, ll;
-    csplit(x0[j], hh, mm, ll);
+    split3(x0[j], hh, mm, ll);
     h[j] = hh;
     m[j] = mm;
     l[j] = ll;
-    csplit(x1[j], hh, mm, ll);
+    split3(x1[j], hh, mm, ll);
     h[4 + j] = hh;
     m[4 + j] = mm;
     l[4 + j] = ll;
   }
-  b[0] = __builtin_bit_cast(cbf16x8, h);
-  b[1] = __builtin_bit_cast(cbf16x8, m);
-  b[2] = __builtin_bit_cast(cbf16x8, l);
+  b[0] = __builtin_bit_cast(bf16x8, h);
+  b[1] = __builtin_bit_cast(bf16x8, m);
+  b[2] = __builtin_bit_cast(bf16x8, l);
 }
 
-// c += a * b over the split planes, smallest terms first (6 products: every pair with
-// plane(a) + plane(b) <= 2; the dropped ones are below f32 rounding)
-__device__ __forceinline__ f32x4 chain_mfma6(const cbf16x8 (&a)[3], const cbf16x8 (&b)[3], f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
-  return c;
-}
-
+}  // namespace
 }  // namespace trpo

@@ -518,7 +518,11 @@ struct trpo_engine {
     stage = dalloc<float>((size_t)cap * std::max(std::max(wp[0], wp[L]), 2));
     if (f16 && (planes_geom_l0() || rbwd0_geom())) {
       x_ldp = (wp[0] + 63) / 64 * 64;
-      const size_t xp = (size_t)((cap + 255) / 256 * 256) * x_ldp;
+      // rfwd01 / fwd01 load all four 32-column k-blocks of an X plane whatever obs is (rfwd.hip xload: 8 k-steps
+      // through a descriptor with no size; the weight image's rows past obs are zero), so the planes hold four
+      // blocks there: with x_ldp = 64 the loads ran 2 x_mpad rows past the end of the allocation
+      const int x_cols = rfwd01_eligible(L, w.data(), wp.data()) ? std::max(x_ldp, 128) : x_ldp;
+      const size_t xp = (size_t)((cap + 255) / 256 * 256) * x_cols;
       Xh = dalloc<uint16_t>(xp);
       Xl = dalloc<uint16_t>(xp);
       W0b = dalloc<uint16_t>(2 * plane3_f(0));

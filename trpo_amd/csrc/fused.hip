@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
   constexpr int TW0 = (OBC * 16 + FW - 1) / FW;   // owned tiles: obs x hidden
   constexpr int TWH = (16 + FW - 1) / FW;         //              hidden x hidden (NL == 3)
   constexpr int TWL = (8 + FW - 1) / FW;          //              hidden x actions
-  __shared__ cu32x4 wl[CHU];
+  __shared__ u32x4 wl[CHU];
   __shared__ __attribute__((aligned(16))) unsigned short simg[2][3 * PL];   // [act | delta] images
   __shared__ float sb[FW][NL][64];                                         // per-wave bias sums
   __shared__ __attribute__((aligned(16))) float sc[NL][64];               // the tangent's biases c_l
@@ -100,13 +100,13 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
     const int frag = s * 32 + ((g ^ chain_hsw(s)) << 3);
 
     // ---- weight-chunk stream (consumption order = a.tab), as chain.hip ----
-    const cu32x4* img = reinterpret_cast<const cu32x4*>(a.img);
-    cu32x4 wr[NLD];
+    const u32x4* img = reinterpret_cast<const u32x4*>(a.img);
+    u32x4 wr[NLD];
     int q = 0;
     auto gload = [&](int qq) {
       qq = qq < a.nchunks ? qq : a.nchunks - 1;
       const int off = a.tab[2 * qq], sz = a.tab[2 * qq + 1];
-      const cu32x4* src = img + off;
+      const u32x4* src = img + off;
 #pragma unroll
       for (int i = 0; i < NLD; ++i) {
         const int idx = tid + i * NT;
@@ -130,56 +130,56 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
     // ---- image helpers ----
     // acc-layout tile t of this lane (features 16t + 4g.., state lrow) -> 3 planes
     auto put4 = [&](unsigned short* slot, int t, const f32x4& x) {
-      cu16x4 h, m, l;
+      u16x4 h, m, l;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         unsigned short hh, mm, ll;
-        csplit(x[j], hh, mm, ll);
+        split3(x[j], hh, mm, ll);
         h[j] = hh;
         m[j] = mm;
         l[j] = ll;
       }
       const int o = fimg(lrow, 16 * t + 4 * g);
-      *reinterpret_cast<cu16x4*>(slot + o) = h;
-      *reinterpret_cast<cu16x4*>(slot + PL + o) = m;
-      *reinterpret_cast<cu16x4*>(slot + 2 * PL + o) = l;
+      *reinterpret_cast<u16x4*>(slot + o) = h;
+      *reinterpret_cast<u16x4*>(slot + PL + o) = m;
+      *reinterpret_cast<u16x4*>(slot + 2 * PL + o) = l;
     };
     // the f32 values of acc-layout tile t of this lane back from the 3 planes (exact: hi + mid + lo)
     auto get4 = [&](const unsigned short* slot, int t) -> f32x4 {
       const int o = fimg(lrow, 16 * t + 4 * g);
-      const cu16x4 h = *reinterpret_cast<const cu16x4*>(slot + o);
-      const cu16x4 m = *reinterpret_cast<const cu16x4*>(slot + PL + o);
-      const cu16x4 l = *reinterpret_cast<const cu16x4*>(slot + 2 * PL + o);
+      const u16x4 h = *reinterpret_cast<const u16x4*>(slot + o);
+      const u16x4 m = *reinterpret_cast<const u16x4*>(slot + PL + o);
+      const u16x4 l = *reinterpret_cast<const u16x4*>(slot + 2 * PL + o);
       f32x4 r;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) r[j] = (cb_val(h[j]) + cb_val(m[j])) + cb_val(l[j]);
+      for (int j = 0; j < 4; ++j) r[j] = (bf16_val(h[j]) + bf16_val(m[j])) + bf16_val(l[j]);
       return r;
     };
     // chain B operand of chunk c (tiles 2c, 2c+1) -> 3 planes
-    auto putb = [&](unsigned short* slot, int c, const cbf16x8 (&b)[3]) {
+    auto putb = [&](unsigned short* slot, int c, const bf16x8 (&b)[3]) {
       const int o0 = fimg(lrow, 32 * c + 4 * g), o1 = fimg(lrow, 32 * c + 16 + 4 * g);
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
-        const cu16x8 v = __builtin_bit_cast(cu16x8, b[p]);
-        *reinterpret_cast<cu16x4*>(slot + p * PL + o0) = cu16x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<cu16x4*>(slot + p * PL + o1) = cu16x4{v[4], v[5], v[6], v[7]};
+        const u16x8 v = __builtin_bit_cast(u16x8, b[p]);
+        *reinterpret_cast<u16x4*>(slot + p * PL + o0) = u16x4{v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<u16x4*>(slot + p * PL + o1) = u16x4{v[4], v[5], v[6], v[7]};
       }
     };
     // 16x16x32 operand of feature tile ft, k-step ks: lane (i = lane&15, g) <- states 32ks + 8g .. +7
     const int tq = (lane >> 2) & 3, tp = lane & 3;
-    auto tfrag = [&](const unsigned short* slot, int ft, int ks, cbf16x8 (&f)[3]) {
+    auto tfrag = [&](const unsigned short* slot, int ft, int ks, bf16x8 (&f)[3]) {
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
-        fs8 v;
+        s16x8 v;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int r = 32 * ks + 8 * g + 4 * t + tq;
-          const fs4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) fs4*)(slot + p * PL + fimg(r, 16 * ft + 4 * tp)));
+          const s16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) s16x4*)(slot + p * PL + fimg(r, 16 * ft + 4 * tp)));
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[4 * t + e] = x[e];
         }
-        f[p] = __builtin_bit_cast(cbf16x8, v);
+        f[p] = __builtin_bit_cast(bf16x8, v);
       }
     };
     // gradient products of this wave's tiles of a layer (TI x TJ tiles) whose act tile lies in
@@ -194,10 +194,10 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
           f32x4 c = dacc[k];
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            cbf16x8 fa_[3], fd_[3];
+            bf16x8 fa_[3], fd_[3];
             tfrag(sA, it - ti0, ks, fa_);
             tfrag(sD, jt, ks, fd_);
-            c = chain_mfma6(fa_, fd_, c);
+            c = mfma6(fa_, fd_, c);
             __builtin_amdgcn_sched_barrier(0);
           }
           dacc[k] = c;
@@ -236,27 +236,27 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
     };
     auto bias4 = [&](int l, int t) -> f32x4 { return *reinterpret_cast<const f32x4*>(&sc[l][16 * t + 4 * g]); };
 
-    auto mma_tile = [&](const unsigned short* W, int pl, int ot, const cbf16x8 (&b)[3]) __attribute__((always_inline)) {
-      cbf16x8 w3[3];
-      w3[0] = *reinterpret_cast<const cbf16x8*>(W + ot * 512);
-      w3[1] = *reinterpret_cast<const cbf16x8*>(W + pl + ot * 512);
-      w3[2] = *reinterpret_cast<const cbf16x8*>(W + 2 * pl + ot * 512);
-      acc[ot] = chain_mfma6(w3, b, acc[ot]);
+    auto mma_tile = [&](const unsigned short* W, int pl, int ot, const bf16x8 (&b)[3]) __attribute__((always_inline)) {
+      bf16x8 w3[3];
+      w3[0] = *reinterpret_cast<const bf16x8*>(W + ot * 512);
+      w3[1] = *reinterpret_cast<const bf16x8*>(W + pl + ot * 512);
+      w3[2] = *reinterpret_cast<const bf16x8*>(W + 2 * pl + ot * 512);
+      acc[ot] = mfma6(w3, b, acc[ot]);
     };
-    auto mma = [&](int OT, const cbf16x8 (&b)[3]) __attribute__((always_inline)) {
+    auto mma = [&](int OT, const bf16x8 (&b)[3]) __attribute__((always_inline)) {
       const unsigned short* W = reinterpret_cast<const unsigned short*>(&wl[0]) + frag;
       const int pl = OT * 512;   // u16 per plane
       if (OT == OTM) {
-        cbf16x8 f[3], nx[3];
+        bf16x8 f[3], nx[3];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const cbf16x8*>(W + p * pl);
+        for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const bf16x8*>(W + p * pl);
 #pragma unroll
         for (int ot = 0; ot < OTM; ++ot) {
           if (ot + 1 < OTM) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) nx[p] = *reinterpret_cast<const cbf16x8*>(W + p * pl + (ot + 1) * 512);
+            for (int p = 0; p < 3; ++p) nx[p] = *reinterpret_cast<const bf16x8*>(W + p * pl + (ot + 1) * 512);
           }
-          acc[ot] = chain_mfma6(f, b, acc[ot]);
+          acc[ot] = mfma6(f, b, acc[ot]);
           if (ot + 1 < OTM) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) f[p] = nx[p];
@@ -298,7 +298,7 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
         m1 = mld(1, 1);
       }
       auto seg0_chunk = [&](int c, int kcc) __attribute__((always_inline)) {
-        cbf16x8 b[3];
+        bf16x8 b[3];
         chain_mkb(S[2 * c], S[2 * c + 1], b);
         chunk_begin();
         if (c == kcc - RING) {
@@ -331,7 +331,7 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
 #pragma unroll
           for (int t = 0; t < OTM; ++t) PF[t] = ld4(rp, t < OTp ? voff(ldp, t) : rb * ldp * 4);
         }
-        cbf16x8 b[3];
+        bf16x8 b[3];
         chain_mkb(x0, x1, b);
         if (cap && c < 2) putb(cap, c, b);
         mma(OT, b);
@@ -371,7 +371,7 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
           const f32x4 cb = bias4(l, t);
           const f32x4 h = PF[t];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) r[i] = c_one_minus_sq(h[i]) * (acc[t][i] + cb[i]);
+          for (int i = 0; i < 4; ++i) r[i] = one_minus_sq(h[i]) * (acc[t][i] + cb[i]);
         }
         S[t] = r;
         RHk[j][t] = r;
@@ -456,7 +456,7 @@ __global__ void __launch_bounds__(FW * 64, FUSED_LB) fvp_fused_kernel(const Fuse
         if (t < OT) {
           const f32x4 h = get4(sA, t), e = PF[t], rh = RHk[l][t];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) r[i] = fmaf(e[i], rh[i], acc[t][i] * c_one_minus_sq(h[i]));
+          for (int i = 0; i < 4; ++i) r[i] = fmaf(e[i], rh[i], acc[t][i] * one_minus_sq(h[i]));
         }
         S[t] = r;
       }

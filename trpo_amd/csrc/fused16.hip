@@ -9,7 +9,7 @@
 // one slab per workgroup) with three differences:
 //
 //  * Arithmetic.  Every product runs on v_mfma_f32_16x16x32_f16 with each f32 operand scaled by a power of
-//    two and split into f16 hi + lo (3 products, 2^-21 relative per operand; gemm.hip rowgemm3 / tail.hip),
+//    two and split into f16 hi + lo (3 products; split.h),
 //    where fused.hip takes 6 bf16 products.  Half the MFMAs, 2/3 of the image and weight-chunk bytes.
 //  * Scales.  Weights: one exponent per image job, set by the image builder from the job's max |w|.
 //    X, D_1, D_2: the engine's running-max slots.  H: fixed (|tanh| <= 1).  Values produced in the launch
@@ -24,7 +24,6 @@
 //
 // States past the shard end read zeros (buffer descriptors): their D / RD and contributions are exactly 0.
 #include "chain_common.h"
-#include "rowepi.h"
 
 #include <algorithm>
 #include <stdexcept>
@@ -63,34 +62,13 @@
 namespace trpo {
 namespace {
 
-typedef _Float16 fh8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned cu32x2 __attribute__((ext_vector_type(2)));
-
-// (a, b) * 1 -> packed f16 hi pair and lo pair, round toward zero: a - hi is exact in f32 and below
-// ulp16(a), so hi + lo is within 2^-21 |a| (tail.hip split8)
-// (returned as {hi pair, lo pair})
-__device__ __forceinline__ cu32x2 split2(float a, float b) {
-  const fp16x2 hp = __builtin_amdgcn_cvt_pkrtz(a, b);
-  const fp16x2 lp = __builtin_amdgcn_cvt_pkrtz(a - (float)hp[0], b - (float)hp[1]);
-  return cu32x2{__builtin_bit_cast(unsigned, hp), __builtin_bit_cast(unsigned, lp)};
-}
-
 // B operand (hi, lo) of v_mfma_f32_16x16x32_f16 from two acc-layout tiles times s (chain_mkb's k order)
-__device__ __forceinline__ void mkb16(const f32x4& x0, const f32x4& x1, float s, fh8 (&b)[2]) {
-  const cu32x2 p0 = split2(x0[0] * s, x0[1] * s), p1 = split2(x0[2] * s, x0[3] * s);
-  const cu32x2 p2 = split2(x1[0] * s, x1[1] * s), p3 = split2(x1[2] * s, x1[3] * s);
-  const cu32x4 H = {p0[0], p1[0], p2[0], p3[0]}, L = {p0[1], p1[1], p2[1], p3[1]};
-  b[0] = __builtin_bit_cast(fh8, H);
-  b[1] = __builtin_bit_cast(fh8, L);
-}
-
-// c += a b over the split: al bh + ah bl + ah bh, smallest terms first
-__device__ __forceinline__ f32x4 mfma3(const fh8 (&a)[2], const fh8 (&b)[2], f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], c, 0, 0, 0);
-  return c;
+__device__ __forceinline__ void mkb16(const f32x4& x0, const f32x4& x1, float s, f16x8 (&b)[2]) {
+  const u32x2 p0 = split2(x0[0] * s, x0[1] * s), p1 = split2(x0[2] * s, x0[3] * s);
+  const u32x2 p2 = split2(x1[0] * s, x1[1] * s), p3 = split2(x1[2] * s, x1[3] * s);
+  const u32x4 H = {p0[0], p1[0], p2[0], p3[0]}, L = {p0[1], p1[1], p2[1], p3[1]};
+  b[0] = __builtin_bit_cast(f16x8, H);
+  b[1] = __builtin_bit_cast(f16x8, L);
 }
 
 __device__ __forceinline__ f32x4 ldexp4(const f32x4& x, int e) {
@@ -161,16 +139,16 @@ __global__ void __launch_bounds__(256) fused16_img_kernel(const ChainImgArgs a, 
   const float sc = __builtin_ldexpf(1.0f, e);
 #pragma unroll
   for (int q = 0; q < 8; ++q) x[q] *= sc;
-  cu32x4 H, L;
+  u32x4 H, L;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const cu32x2 p = split2(x[2 * i], x[2 * i + 1]);
+    const u32x2 p = split2(x[2 * i], x[2 * i + 1]);
     H[i] = p[0];
     L[i] = p[1];
   }
   unsigned short* dst = a.img + j.dst_off + (size_t)c * 2 * j.otp * 32 + o * 32 + ((gg ^ chain_hsw(o)) << 3);
-  *reinterpret_cast<cu32x4*>(dst) = H;
-  *reinterpret_cast<cu32x4*>(dst + (size_t)j.otp * 32) = L;
+  *reinterpret_cast<u32x4*>(dst) = H;
+  *reinterpret_cast<u32x4*>(dst + (size_t)j.otp * 32) = L;
 }
 
 // The CG's p update (utils.py:196-198, vec.hip cg_p_kernel) fused with the next FVP's V images (fused16_img_kernel,
@@ -239,16 +217,16 @@ __global__ void __launch_bounds__(256) cg_p_img16_kernel(const ChainImgArgs a, c
   const float sc2 = __builtin_ldexpf(1.0f, e);
 #pragma unroll
   for (int q = 0; q < 8; ++q) x[q] *= sc2;
-  cu32x4 H, L;
+  u32x4 H, L;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const cu32x2 pp = split2(x[2 * i], x[2 * i + 1]);
+    const u32x2 pp = split2(x[2 * i], x[2 * i + 1]);
     H[i] = pp[0];
     L[i] = pp[1];
   }
   unsigned short* dst = a.img + j.dst_off + (size_t)c * 2 * j.otp * 32 + o * 32 + ((gg ^ chain_hsw(o)) << 3);
-  *reinterpret_cast<cu32x4*>(dst) = H;
-  *reinterpret_cast<cu32x4*>(dst + (size_t)j.otp * 32) = L;
+  *reinterpret_cast<u32x4*>(dst) = H;
+  *reinterpret_cast<u32x4*>(dst + (size_t)j.otp * 32) = L;
 }
 
 // image jobs (kernels.h, kFused16Jobs): NH = 2: V_0 | W_1 V_1 | W_2 V_2 | W_2^T V_2^T | W_1^T V_1^T;
@@ -283,7 +261,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
   constexpr int RING = FUSED16_RING;
   // weight-chunk ring: FUSED16_DMA: three slots, chunk q of a group in slot q % 3 (three distinct objects, so the
   // compiler's LDS-DMA wait before a slot's first read counts only the DMA into that slot); else two buffers
-  __shared__ cu32x4 wl0[CHU], wl1[CHU], wl2[FUSED16_DMA ? CHU : 1];
+  __shared__ u32x4 wl0[CHU], wl1[CHU], wl2[FUSED16_DMA ? CHU : 1];
   __shared__ __attribute__((aligned(16))) unsigned short simg[2][2 * PL];   // [act | delta] images, hi / lo planes
   __shared__ float sb[FW][3][64];                                          // per-wave bias sums
   __shared__ __attribute__((aligned(16))) float sc[3][64];                // the tangent's biases c_l
@@ -340,13 +318,13 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
   // W_2^T (one chunk) and W_1^T (two); with one hidden layer W_1^T (one chunk: K = actions)
   auto chunk_of = [&](int q) { return PG ? (NH == 1 ? KX + 4 : q == 0 ? KX + 8 : KX + 9 + q) : q; };
   constexpr int WS = FUSED16_DMA ? 1 : FUSED16_WSETS;
-  cu32x4 wr[WS][NLD];
+  u32x4 wr[WS][NLD];
   // ---- LDS-DMA weight stream (FUSED16_DMA): chunk q of a group is DMA'd into slot q % 3 at chunk q - 2's begin
   // (after its barrier: every wave is past chunk q - 3, the slot's last reader).  The next group's chunk j (0, 1)
   // goes to slot j when one of the current group's last two chunks frees it (both do when NCH % 3 == 0: C2, C3),
   // else at its group's start.  Each wave-instruction moves 1 KB: lanes -> consecutive 16-B units, the image's
   // own layout. ----
-  auto slot = [&](int k) -> cu32x4* { return k % 3 == 0 ? wl0 : k % 3 == 1 ? wl1 : wl2; };
+  auto slot = [&](int k) -> u32x4* { return k % 3 == 0 ? wl0 : k % 3 == 1 ? wl1 : wl2; };
   auto dma = [&](int sl, int qq, bool from_lds = true) __attribute__((always_inline)) {
     if constexpr ((FUSED16_ABL & 4) != 0) return;   // ablation: no weight-chunk loads
     const int off = __builtin_amdgcn_readfirstlane(from_lds ? stab[2 * qq] : a.tab[2 * qq]);
@@ -370,7 +348,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
       for (int i = 0; i < NLD; ++i) {
         unsigned u = qq + i;
         asm volatile("" : "+v"(u));
-        wr[set][i] = cu32x4{u, u, u, u};
+        wr[set][i] = u32x4{u, u, u, u};
       }
       return;
     }
@@ -380,7 +358,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
     for (int i = 0; i < NLD; ++i) {
       const int idx = threadIdx.x + i * NT;
       wr[set][i] = __builtin_bit_cast(
-          cu32x4, __builtin_amdgcn_raw_buffer_load_b128(rimg, (idx < sz ? idx : sz - 1) * 16, off * 16, 0));
+          u32x4, __builtin_amdgcn_raw_buffer_load_b128(rimg, (idx < sz ? idx : sz - 1) * 16, off * 16, 0));
     }
   };
   if constexpr (FUSED16_DMA) {   // (the table's LDS copy is not visible before the first barrier)
@@ -416,9 +394,9 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
     const bool more = grp + (int)gridDim.x < ngroups;   // a next group (uniform)
     auto chunk_begin_dma = [&]() __attribute__((always_inline)) {
       __builtin_amdgcn_sched_barrier(0);
-      cu32x4* buf = slot(q);
+      u32x4* buf = slot(q);
       // this wave's DMA into the slot has landed (the compiler's LDS-DMA wait, placed before this read) ...
-      cu32x4 probe = buf[threadIdx.x];
+      u32x4 probe = buf[threadIdx.x];
       asm volatile("" ::"v"(probe));
       // ... and every wave's: chunk q visible; every wave is past chunk q - 1 (slot (q + 2) % 3's last reader)
       lds_barrier();
@@ -436,7 +414,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
         return;
       }
       __builtin_amdgcn_sched_barrier(0);
-      cu32x4* buf = slot(q & 1);
+      u32x4* buf = slot(q & 1);
 #pragma unroll
       for (int i = 0; i < NLD; ++i) {
         const int idx = threadIdx.x + i * NT;
@@ -450,35 +428,35 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
 
     // ---- image helpers (planes hi, lo; each image holds values times one power of two) ----
     auto put4 = [&](unsigned short* slot, int t, const f32x4& x, float m) {
-      const cu32x2 p0 = split2(x[0] * m, x[1] * m), p1 = split2(x[2] * m, x[3] * m);
+      const u32x2 p0 = split2(x[0] * m, x[1] * m), p1 = split2(x[2] * m, x[3] * m);
       const int o = fimg(lrow, 16 * t + 4 * g);
-      *reinterpret_cast<cu32x2*>(slot + o) = cu32x2{p0[0], p1[0]};
-      *reinterpret_cast<cu32x2*>(slot + PL + o) = cu32x2{p0[1], p1[1]};
+      *reinterpret_cast<u32x2*>(slot + o) = u32x2{p0[0], p1[0]};
+      *reinterpret_cast<u32x2*>(slot + PL + o) = u32x2{p0[1], p1[1]};
     };
-    auto putb = [&](unsigned short* slot, int c, const fh8 (&b)[2]) {   // a B operand of chunk c
+    auto putb = [&](unsigned short* slot, int c, const f16x8 (&b)[2]) {   // a B operand of chunk c
       const int o0 = fimg(lrow, 32 * c + 4 * g), o1 = fimg(lrow, 32 * c + 16 + 4 * g);
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        const cu32x4 v = __builtin_bit_cast(cu32x4, b[p]);
-        *reinterpret_cast<cu32x2*>(slot + p * PL + o0) = cu32x2{v[0], v[1]};
-        *reinterpret_cast<cu32x2*>(slot + p * PL + o1) = cu32x2{v[2], v[3]};
+        const u32x4 v = __builtin_bit_cast(u32x4, b[p]);
+        *reinterpret_cast<u32x2*>(slot + p * PL + o0) = u32x2{v[0], v[1]};
+        *reinterpret_cast<u32x2*>(slot + p * PL + o1) = u32x2{v[2], v[3]};
       }
     };
     // 16x16x32 operand of feature tile ft, k-step ks: lane (i = lane & 15, g) <- states 32ks + 8g .. +7
     const int tq = (lane >> 2) & 3, tp = lane & 3;
-    auto tfrag = [&](const unsigned short* slot, int ft, int ks, fh8 (&f)[2]) {
+    auto tfrag = [&](const unsigned short* slot, int ft, int ks, f16x8 (&f)[2]) {
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        fs8 v;
+        s16x8 v;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int r = 32 * ks + 8 * g + 4 * t + tq;
-          const fs4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) fs4*)(slot + p * PL + fimg(r, 16 * ft + 4 * tp)));
+          const s16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) s16x4*)(slot + p * PL + fimg(r, 16 * ft + 4 * tp)));
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[4 * t + e] = x[e];
         }
-        f[p] = __builtin_bit_cast(fh8, v);
+        f[p] = __builtin_bit_cast(f16x8, v);
       }
     };
     // gradient products of this wave's tiles of a TI x TJ layer whose act tile lies in [ti0, ti0 + 4),
@@ -495,7 +473,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
           f32x4 c = z4;
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            fh8 fa_[2], fd_[2];
+            f16x8 fa_[2], fd_[2];
             tfrag(sA, it - ti0, ks, fa_);
             tfrag(sD, jt, ks, fd_);
             c = mfma3(fa_, fd_, c);
@@ -552,21 +530,21 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
       return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, vo, 0, 0));
     };
     auto st4 = [&](float* p, int ld, int t, const f32x4& x) {   // acc-layout tile t of this lane's state row
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cu32x4, x), rsrc(p, ld), voff(ld, t), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rsrc(p, ld), voff(ld, t), 0, 0);
     };
     auto bias4 = [&](int l, int t) -> f32x4 { return *reinterpret_cast<const f32x4*>(&sc[l][16 * t + 4 * g]); };
 
-    auto mma_to = [&](auto OT_, const fh8 (&b)[2], f32x4 (&ac)[OTM]) __attribute__((always_inline)) {
+    auto mma_to = [&](auto OT_, const f16x8 (&b)[2], f32x4 (&ac)[OTM]) __attribute__((always_inline)) {
       constexpr int OT = decltype(OT_)::value;
       constexpr int pl = OT * 512;   // u16 per plane of the chunk
-      fh8 f[2], nx[2];
+      f16x8 f[2], nx[2];
 #pragma unroll
-      for (int p = 0; p < 2; ++p) f[p] = *reinterpret_cast<const fh8*>(W + p * pl);
+      for (int p = 0; p < 2; ++p) f[p] = *reinterpret_cast<const f16x8*>(W + p * pl);
 #pragma unroll
       for (int ot = 0; ot < OT; ++ot) {
         if (ot + 1 < OT) {
 #pragma unroll
-          for (int p = 0; p < 2; ++p) nx[p] = *reinterpret_cast<const fh8*>(W + p * pl + (ot + 1) * 512);
+          for (int p = 0; p < 2; ++p) nx[p] = *reinterpret_cast<const f16x8*>(W + p * pl + (ot + 1) * 512);
         }
         ac[ot] = mfma3(f, b, ac[ot]);
         if (ot + 1 < OT) {
@@ -576,7 +554,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
       }
     };
 
-    auto mma = [&](auto OT_, const fh8 (&b)[2]) __attribute__((always_inline)) { mma_to(OT_, b, acc); };
+    auto mma = [&](auto OT_, const f16x8 (&b)[2]) __attribute__((always_inline)) { mma_to(OT_, b, acc); };
     auto no_extra = [](int) {};
 
     // One chain step: acc = [S (KC0 chunks, registers, times 2^eS per state) x job jS |
@@ -620,7 +598,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
         const float sS = __builtin_amdgcn_ldexpf(1.0f, eS);
 #pragma unroll
         for (int c = 0; c < KC0; ++c) {
-          fh8 b[2];
+          f16x8 b[2];
           mkb16(S[2 * c], S[2 * c + 1], sS, b);
           chunk_begin();
 #pragma unroll
@@ -641,7 +619,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
         chunk_begin();
         if (c + RING < KC1 && KC0 + c + RING >= RING) issue(c + RING);
         if (!FUSED16_PFEARLY && c == 0) pf_load();
-        fh8 b[2];
+        f16x8 b[2];
         mkb16(mb[c][0], mb[c][1], sM, b);
         if (cap) putb(cap, c, b);
         mma(OT_, b);
@@ -679,7 +657,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
       }
       auto extra1 = [&](int) {
         if constexpr (PREP) {
-          fh8 b[2];
+          f16x8 b[2];
           mkb16(d2c0, d2c1, sDh, b);
           mma_to(C4{}, b, accD);
         }
@@ -694,14 +672,14 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
         const f32x4 h = PF[t];
         if constexpr (NH == 1) H1f[t] = h;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) DS1[t][i] = acc[t][i] * (su * c_one_minus_sq(h[i]));
+        for (int i = 0; i < 4; ++i) DS1[t][i] = acc[t][i] * (su * one_minus_sq(h[i]));
         put4(sA, t, h, sH);   // H_NH, the head layer's pass operand (sA is free: past this step's chunk barrier)
         if constexpr (PREP) {
           f32x4 e1;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const float dh = accD[t][i] * suD;
-            D1v[t][i] = dh * c_one_minus_sq(h[i]);
+            D1v[t][i] = dh * one_minus_sq(h[i]);
             e1[i] = -2.0f * dh * h[i];
           }
           if constexpr (NH == 2) {
@@ -725,7 +703,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
         const float sD1s = __builtin_ldexpf(1.0f, f16_scale_exp(mstD));
         auto extra2 = [&](int c) {
           if constexpr (PREP) {
-            fh8 b[2];
+            f16x8 b[2];
             mkb16(D1v[2 * c], D1v[2 * c + 1], sD1s, b);
             mma_to(C4{}, b, accD);
           }
@@ -740,7 +718,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
           const f32x4 h = PF[t];
           H1f[t] = h;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) S[t][i] = acc[t][i] * (su * c_one_minus_sq(h[i]));   // DS_0
+          for (int i = 0; i < 4; ++i) S[t][i] = acc[t][i] * (su * one_minus_sq(h[i]));   // DS_0
           if constexpr (PREP) {
             f32x4 e0;
 #pragma unroll
@@ -822,7 +800,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
     for (int t = 0; t < OTM; ++t) {
       const f32x4 cb = bias4(0, t), h = PF[t];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) RH1[t][i] = c_one_minus_sq(h[i]) * __builtin_fmaf(acc[t][i], su, cb[i]);
+      for (int i = 0; i < 4; ++i) RH1[t][i] = one_minus_sq(h[i]) * __builtin_fmaf(acc[t][i], su, cb[i]);
       H1f[t] = h;   // H_1: the next step's memory segment (FUSED16_REUSE)
     }
     float mst = state_max<OTM>(RH1);
@@ -837,7 +815,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
       for (int t = 0; t < OTM; ++t) {
         const f32x4 cb = bias4(1, t), h = PF[t];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) RH2[t][i] = c_one_minus_sq(h[i]) * __builtin_fmaf(acc[t][i], su, cb[i]);
+        for (int i = 0; i < 4; ++i) RH2[t][i] = one_minus_sq(h[i]) * __builtin_fmaf(acc[t][i], su, cb[i]);
         H2f[t] = h;
       }
       mst = state_max<OTM>(RH2);
@@ -922,7 +900,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
     for (int t = 0; t < OTM; ++t) {
       const f32x4 h = Htf[t], e = PF[t];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) S[t][i] = __builtin_fmaf(e[i], RHt[t][i], acc[t][i] * (su * c_one_minus_sq(h[i])));
+      for (int i = 0; i < 4; ++i) S[t][i] = __builtin_fmaf(e[i], RHt[t][i], acc[t][i] * (su * one_minus_sq(h[i])));
     }
     mst = state_max<OTM>(S);
     wave_max(NH == 2 ? 3 : 4, mst);
@@ -960,7 +938,7 @@ __global__ void __launch_bounds__(FW * 64, LB) fvp_fused16_kernel(const Fused16A
       for (int t = 0; t < OTM; ++t) {
         const f32x4 h = H1f[t], e = PF[t];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) S[t][i] = __builtin_fmaf(e[i], RH1[t][i], acc[t][i] * (su * c_one_minus_sq(h[i])));
+        for (int i = 0; i < 4; ++i) S[t][i] = __builtin_fmaf(e[i], RH1[t][i], acc[t][i] * (su * one_minus_sq(h[i])));
       }
       mst = state_max<OTM>(S);
       wave_max(4, mst);
@@ -1082,13 +1060,13 @@ __global__ void __launch_bounds__(64 * FWDL16_NW, 2) fwd_loss16_kernel(const Fwd
   constexpr int LH = NH + 1;                   // index of the action width in w[] / ld[]
   constexpr int NCK = KX + 2 * NH;             // W_0 (KX chunks), W_1 (2)[, W_2 (2)]
   constexpr int CHU = 8 * 16 * OTM;            // 16-B units of a full chunk
-  __shared__ cu32x4 wl[NCK][CHU];
+  __shared__ u32x4 wl[NCK][CHU];
   __shared__ __attribute__((aligned(16))) float sbias[3][64];
   if (a.skip && *a.skip) return;
 
   for (int q = 0; q < NCK; ++q) {
     const int off = a.tab[2 * q], sz = a.tab[2 * q + 1];
-    const cu32x4* src = reinterpret_cast<const cu32x4*>(a.img) + off;
+    const u32x4* src = reinterpret_cast<const u32x4*>(a.img) + off;
     for (int i = threadIdx.x; i < sz; i += NT) wl[q][i] = src[i];
   }
   for (int i = threadIdx.x; i < 3 * 64; i += NT) {
@@ -1113,14 +1091,14 @@ __global__ void __launch_bounds__(64 * FWDL16_NW, 2) fwd_loss16_kernel(const Fwd
   // the fragment offset is re-derived per group from an opaque copy: the weight fragments are the same for every
   // group, and hoisted out of the loop they took 200+ registers
   int frag = 0;
-  auto mma_chunk = [&](int q, auto OT_, const fh8 (&b)[2], f32x4 (&ac)[OTM]) __attribute__((always_inline)) {
+  auto mma_chunk = [&](int q, auto OT_, const f16x8 (&b)[2], f32x4 (&ac)[OTM]) __attribute__((always_inline)) {
     constexpr int OT = decltype(OT_)::value, pl = OT * 512;
     const unsigned short* W = reinterpret_cast<const unsigned short*>(&wl[q][0]) + frag;
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot) {
-      fh8 f[2];
+      f16x8 f[2];
 #pragma unroll
-      for (int p = 0; p < 2; ++p) f[p] = *reinterpret_cast<const fh8*>(W + p * pl + ot * 512);
+      for (int p = 0; p < 2; ++p) f[p] = *reinterpret_cast<const f16x8*>(W + p * pl + ot * 512);
       ac[ot] = mfma3(f, b, ac[ot]);
     }
   };
@@ -1158,7 +1136,7 @@ __global__ void __launch_bounds__(64 * FWDL16_NW, 2) fwd_loss16_kernel(const Fwd
     for (int t = 0; t < OTM; ++t) acc[t] = z4;
 #pragma unroll
     for (int c = 0; c < KX; ++c) {
-      fh8 b[2];
+      f16x8 b[2];
       mkb16(xb[c][0], xb[c][1], sX, b);
       mma_chunk(c, C4{}, b, acc);
     }
@@ -1172,7 +1150,7 @@ __global__ void __launch_bounds__(64 * FWDL16_NW, 2) fwd_loss16_kernel(const Fwd
       for (int t = 0; t < nt; ++t) {
         const int col = 16 * t + 4 * g;
         const int vo = col < ld ? (s * ld + col) * 4 : rb * ld * 4;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cu32x4, x[t]), r, vo, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x[t]), r, vo, 0, 0);
       }
     };
     // H_1 = tanh(X W_0 + b_0); padding features: zero weights and bias, tanh(0) = 0
@@ -1187,7 +1165,7 @@ __global__ void __launch_bounds__(64 * FWDL16_NW, 2) fwd_loss16_kernel(const Fwd
     if constexpr (NH == 2) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        fh8 b[2];
+        f16x8 b[2];
         mkb16(H[2 * c], H[2 * c + 1], sH, b);
         mma_chunk(KX + c, C4{}, b, acc);
       }
@@ -1202,7 +1180,7 @@ __global__ void __launch_bounds__(64 * FWDL16_NW, 2) fwd_loss16_kernel(const Fwd
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      fh8 b[2];
+      f16x8 b[2];
       mkb16(H[2 * c], H[2 * c + 1], sH, b);
       mma_chunk(KX + 2 * (NH - 1) + c, COTA{}, b, acc);
     }

@@ -19,30 +19,13 @@
 // k-tile (two LDS buffers).  A/B fragments for 32x32x2: lane l holds
 // A[i = l&31][k] and B[k][j = l&31] with the k of lane half h = l>>5 permuted
 // to 4h + s for k-step s, so A fragments come from one ds_read_b128.
-#include "common.h"
-#include "kernels.h"
-#include <cstdlib>
+#include "rowepi.h"
+
 #include <stdexcept>
 #include <type_traits>
 #include <string>
 
-#include "rowepi.h"
-
 namespace trpo {
-
-static int env_int(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-Options g_options = {env_int("TRPO_SPLIT_MFMA", 5), env_int("TRPO_SPLIT_WG", 1), env_int("TRPO_CHAIN", 1),
-                     env_int("TRPO_SPLIT_F16", 1), env_int("TRPO_SPLIT_MIN_K", 0), env_int("TRPO_GRAPHS", 1),
-                     env_int("TRPO_TAIL", 1), env_int("TRPO_FUSED", 3), env_int("TRPO_LOW_SEG", 14),
-                     env_int("TRPO_PLANES", 1), env_int("TRPO_RBWD0", 1), env_int("TRPO_HBWD2", 2),
-                     env_int("TRPO_HEAD_FWD", 1), env_int("TRPO_SPLITS", 0),
-                     env_int("TRPO_PG_SPLITS", 0), env_int("TRPO_LS_FUSED", 1),
-                     env_int("TRPO_CG_FUSE_REDUCE", 1), env_int("TRPO_CG_P_IMG", 1),
-                     env_int("TRPO_RFWD01", 1), env_int("TRPO_FWD01", 1),
-                     env_int("TRPO_RH1_PLANES", 1)};
 
 namespace {
 
@@ -339,7 +322,7 @@ rowgemm3_kernel(const RowGemmArgs args) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             unsigned short hh, ll;
-            split2h(x[j] * sa, hh, ll);
+            split2_rn(x[j] * sa, hh, ll);
             h[j] = hh;
             l[j] = ll;
           }
@@ -386,15 +369,7 @@ rowgemm3_kernel(const RowGemmArgs args) {
           const int ao = swk(wm * TM * 32 + tm * 32 + lr, 2 * ks + lh);
 #pragma unroll
           for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(As + p * APL + ao);
-          // smallest terms first
-          f32x16 c = acc[tm][tn];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-          acc[tm][tn] = c;
+          acc[tm][tn] = mfma6(a, b, acc[tm][tn]);
         }
       } else {
         f16x8 b[2];
@@ -406,11 +381,7 @@ rowgemm3_kernel(const RowGemmArgs args) {
           const int ao = swk(wm * TM * 32 + tm * 32 + lr, 2 * ks + lh);
 #pragma unroll
           for (int p = 0; p < 2; ++p) a[p] = *reinterpret_cast<const f16x8*>(As + p * APL + ao);
-          f32x16 c = acc[tm][tn];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c, 0, 0, 0);
-          acc[tm][tn] = c;
+          acc[tm][tn] = mfma3(a, b, acc[tm][tn]);
         }
       }
     }
@@ -566,9 +537,6 @@ wgrad3_kernel(const WGradArgs args) {
     const bool okc = (BI % NT == 0 || f < BI) && n0 + c < args.Npad;
     vB[i] = okc ? 8 * g * ldb4 + (n0 + c) * 4 : kOob;
   }
-  auto ldbuf = [](__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
-  };
   struct Stage {
     float va[AP][8], vb[BP][8];
     bool cs;         // this tile belongs to the column-summed segment
@@ -631,7 +599,7 @@ wgrad3_kernel(const WGradArgs args) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         unsigned short hh, ll;
-        split2h(v[q] * sc, hh, ll);
+        split2_rn(v[q] * sc, hh, ll);
         h[q] = hh;
         l[q] = ll;
       }
@@ -661,12 +629,11 @@ wgrad3_kernel(const WGradArgs args) {
       if (AI % NT != 0 && f >= AI) continue;
       if (PA && st.sg == 0) {
         // the planes' dwords are the chunk's 8 rows in order
-        typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
         unsigned short* dst = As + swz16(f % BM, f / BM);
-        *reinterpret_cast<u32x4s*>(dst) = u32x4s{__float_as_uint(st.va[i][0]), __float_as_uint(st.va[i][1]),
+        *reinterpret_cast<u32x4*>(dst) = u32x4{__float_as_uint(st.va[i][0]), __float_as_uint(st.va[i][1]),
                                                  __float_as_uint(st.va[i][2]), __float_as_uint(st.va[i][3])};
         if (!one0)
-          *reinterpret_cast<u32x4s*>(dst + APL) = u32x4s{__float_as_uint(st.va[i][4]), __float_as_uint(st.va[i][5]),
+          *reinterpret_cast<u32x4*>(dst + APL) = u32x4{__float_as_uint(st.va[i][4]), __float_as_uint(st.va[i][5]),
                                                          __float_as_uint(st.va[i][6]), __float_as_uint(st.va[i][7])};
       } else {
         put(As, APL, f % BM, f / BM, st.va[i], eA[st.sg]);
@@ -711,14 +678,7 @@ wgrad3_kernel(const WGradArgs args) {
           const int ao = swz16(wm * TM * 32 + tm * 32 + lr, lh);
 #pragma unroll
           for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(As + p * APL + ao);
-          f32x16 c = acc[tm][tn];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-          acc[tm][tn] = c;
+          acc[tm][tn] = mfma6(a, b, acc[tm][tn]);
         }
       } else {
         f16x8 b[2];
@@ -730,11 +690,7 @@ wgrad3_kernel(const WGradArgs args) {
           const int ao = swz16(wm * TM * 32 + tm * 32 + lr, lh);
 #pragma unroll
           for (int p = 0; p < 2; ++p) a[p] = *reinterpret_cast<const f16x8*>(As + p * APL + ao);
-          f32x16 c = acc[tm][tn];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c, 0, 0, 0);
-          acc[tm][tn] = c;
+          acc[tm][tn] = mfma3(a, b, acc[tm][tn]);
         }
       }
     }
@@ -841,7 +797,7 @@ __global__ void __launch_bounds__(256) split_b_kernel(const SplitArgs a, const i
       const int k = 8 * c + q;
       const float x = k < j.K ? j.B[(size_t)k * j.ldb + n] : 0.0f;
       unsigned short hh, ll;
-      split2h(x * sb, hh, ll);
+      split2_rn(x * sb, hh, ll);
       h[q] = hh;
       l[q] = ll;
     }

@@ -11,8 +11,7 @@
 // are staged in LDS and broadcast, and the next tile's H and deltas are loaded while the current one computes.
 // Sums run k = 0 .. A-1 as f32 fmaf chains (exact f32, as the f32 MFMA row GEMM they replace; the order
 // differs, the rounding level does not).
-#include "common.h"
-#include "kernels.h"
+#include "split.h"
 
 #include <algorithm>
 #include <stdexcept>
@@ -189,10 +188,6 @@ __global__ void __launch_bounds__(kHbThreads) head_bwd2_kernel(const HeadBwd2Arg
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kHmW = 8;   // waves
 
-__device__ __forceinline__ float ldbf(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
-}
-
 template <int K2>   // k-steps of the action contraction: ceil(A / 2)
 __global__ void __launch_bounds__(kHmW * 64, 2) head_bwd2m_kernel(const HeadBwd2Args a) {
   __shared__ float sd[2][kHbRows][kHbA + 1];   // the tile's D2 / DS2 rows, zero past A (pad: conflict-free reads)
@@ -227,14 +222,14 @@ __global__ void __launch_bounds__(kHmW * 64, 2) head_bwd2m_kernel(const HeadBwd2
   auto load = [&](int t0, float (&hv)[16], float (&pv)[kSt]) {
     const __amdgpu_buffer_rsrc_t rH = desc(a.H, t0, a.Npad, 4);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) hv[i] = ldbf(rH, vo, roff(i) * a.Npad * 4);
+    for (int i = 0; i < 16; ++i) hv[i] = ldbuf(rH, vo, roff(i) * a.Npad * 4);
     const __amdgpu_buffer_rsrc_t rD = desc(a.D2, t0, a.Apad, 4), rS = desc(a.DS2, t0, a.Apad, 4);
 #pragma unroll
     for (int u = 0; u < kSt; ++u) {
       const int i = tid + u * kHmW * 64;
       const int m = i / (kHbRows * kHbA), r = (i / kHbA) % kHbRows, j = i % kHbA;
       const int v = j < a.A ? (r * a.Apad + j) * 4 : kOob;
-      pv[u] = ldbf(m ? rS : rD, v, 0);
+      pv[u] = ldbuf(m ? rS : rD, v, 0);
     }
   };
   if (r0 < r1) load(r0, hc, pc);

@@ -10,11 +10,8 @@
 
 namespace trpo {
 
-// Kernel-variant switches (defaults from TRPO_SPLIT_MFMA, TRPO_SPLIT_WG, TRPO_CHAIN, TRPO_SPLIT_F16,
-// TRPO_SPLIT_MIN_K, TRPO_GRAPHS, TRPO_TAIL, TRPO_FUSED, TRPO_LOW_SEG, TRPO_PLANES, TRPO_RBWD0, TRPO_HBWD2,
-// TRPO_HEAD_FWD, TRPO_SPLITS, TRPO_PG_SPLITS, TRPO_LS_FUSED, TRPO_CG_FUSE_REDUCE, TRPO_CG_P_IMG, TRPO_RFWD01,
-// TRPO_FWD01, TRPO_RH1_PLANES in gemm.hip, in the order of the fields; runtime-settable through trpo_set_option for A/B and
-// parity tests).
+// Kernel-variant switches.  Names, environment variables (TRPO_<NAME>) and defaults are the rows of
+// options.cpp's table; runtime-settable through trpo_set_option for A/B and parity tests.
 struct Options {
   int split_mfma;  // row GEMMs with N > 128 on the split MFMA: 0 off (f32 MFMA), 5 = 256 x 256 tile at
                    // BK 32 on f16 planes (default), 6 = 256 x 256 at BK 16, any other value = 128 x 256
@@ -73,6 +70,7 @@ __host__ __device__ inline int f16_scale_exp(float m) {
   return e < -100 ? -100 : (e > 100 ? 100 : e);
 }
 extern Options g_options;
+int* option_slot(const char* name);   // the field of g_options called `name`; NULL: no such option
 
 // ---------------------------------------------------------------------------
 // Row GEMM:  C[M x N] = sum_seg A_seg[M x K_seg] * B_seg[K_seg x Npad]  -> epilogue
@@ -660,6 +658,7 @@ struct Rfwd01Args {
   int64_t n;
   int obs, ldh, ldz;                 // obs; row strides of H1 / RH1 and of RZ2 (floats)
   const uint16_t *Xh, *Xl;           // X's k-blocked f16 planes (GemmSeg::Ah), x_mpad rows per 32-k block
+                                     // (all four blocks are loaded whatever obs is: 128 x_mpad values per plane)
   int x_mpad;
   const int* eX;                     // their scale exponent
   const float *H1, *c0, *c1;         // H1; the tangent biases of layers 0 and 1 (v + offb[l])
@@ -682,6 +681,7 @@ struct Fwd01Args {
   int64_t n;
   int obs;
   const uint16_t *Xh, *Xl;           // X's k-blocked f16 planes, x_mpad rows per 32-k block
+                                     // (four blocks, as Rfwd01Args)
   int x_mpad;
   const int* eX;
   const float *b0, *b1;              // th + offb[0], th + offb[1]

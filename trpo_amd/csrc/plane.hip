@@ -76,32 +76,19 @@ __device__ __forceinline__ void pl_compute(const unsigned char* As, const unsign
         const f16x8 bh = *reinterpret_cast<const f16x8*>(Bs + off);
         const f16x8 bl = *reinterpret_cast<const f16x8*>(Bs + kPlSub + off);
 #pragma unroll
-        for (int tm = 0; tm < TM; ++tm) {
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[tm], bh, acc[tm][tn], 0, 0, 0);
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[tm], bl, acc[tm][tn], 0, 0, 0);
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[tm], bh, acc[tm][tn], 0, 0, 0);
-        }
+        for (int tm = 0; tm < TM; ++tm)
+          acc[tm][tn] = mfma3(ah[tm], al[tm], bh, bl, acc[tm][tn]);
       }
     }
   }
 }
 
-// The four DMAs of one wave for one operand of one stage, as buffer_load_dwordx4 ... lds: `rsrc` starts at
-// this wave's first row (a contiguous 4 KB run of one k-block), instruction i moves the KB at i KB; `voff`
-// is the lane's (swizzled) offset within a KB and `lds0` the uniform LDS byte address of the wave's first
-// KB of the slot (M0; the destination is lane-linear).
+// The four DMAs (split.h dma16) of one wave for one operand of one stage: `rsrc` starts at this wave's first row
+// (a contiguous 4 KB run of one k-block), instruction i moves the KB at i KB; `voff` is the lane's (swizzled)
+// offset within a KB and `lds0` the uniform LDS byte address of the wave's first KB of the slot.
 __device__ __forceinline__ void pl_dma4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned lds0) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    unsigned keep;
-    // M0 is saved and restored around the DMA (the compiler owns it).  No "memory" clobber: the DMA writes
-    // a ring slot that no fragment read of this stage touches, __syncthreads's fences order it against the
-    // reads of other stages, and a clobber would pin every address-taken local to the stack.
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(rsrc), "s"(lds0 + 1024u * i), "s"(1024 * i));
-  }
+  for (int i = 0; i < 4; ++i) dma16(rsrc, voff, 1024u * i, lds0 + 1024u * i);
 }
 
 // NSEG: 1 (layer 0's X-only GEMMs: no second-segment loops or one-product variants to keep registers for)

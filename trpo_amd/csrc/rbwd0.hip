@@ -31,7 +31,7 @@
 //     D_1's plane is attached) the epilogue reads RH_1's hi plane alone, 2 B per element instead of 4, and
 //     otherwise hi + lo (22 bits at the planes' one exponent).  A plane dword holds rows r, r + 1 of a column:
 //     the accumulator registers 2 i, 2 i + 1 of this lane, so a chunk of 4 registers takes 2 loads, not 4.
-#include "rowepi.h"
+#include "split.h"
 #include <stdexcept>
 #include <type_traits>
 
@@ -101,45 +101,9 @@ __device__ __forceinline__ int xoff(int row, int ch) {
   return 2048 * (row >> 3) + 512 * (ch >> 2) + 64 * (row & 7) + 16 * ((ch & 3) ^ ((row >> 2) & 3));
 }
 
-// one 16-B-per-lane LDS-DMA (buffer_load_dwordx4 ... lds): lane-linear destination at the wave-uniform LDS
-// byte address `lds`, per-lane source offset `voff` in the descriptor `rsrc` (M0 saved and restored)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned lds) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(lds), "s"(0u));
-}
-
 #ifndef R0_ABL
 #define R0_ABL 0   // timing ablations only (A/B builds): 1 no X^T RD_0 phase, 2 no epilogue loads, 3 no k-loop
 #endif
-typedef short s4 __attribute__((ext_vector_type(4)));
-typedef short s8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-
-// x * 2^e -> f16 hi + lo for 8 values (round toward zero: x - hi exact, hi + lo within 2^-21 |x|)
-__device__ __forceinline__ void split8h(const float* x, float s, f16x8& hi, f16x8& lo) {
-  typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-  u32x4v H, L;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i] * s, b = x[2 * i + 1] * s;
-    const fp16x2 hp = __builtin_amdgcn_cvt_pkrtz(a, b);
-    const fp16x2 lp = __builtin_amdgcn_cvt_pkrtz(a - (float)hp[0], b - (float)hp[1]);
-    H[i] = __builtin_bit_cast(unsigned, hp);
-    L[i] = __builtin_bit_cast(unsigned, lp);
-  }
-  hi = __builtin_bit_cast(f16x8, H);
-  lo = __builtin_bit_cast(f16x8, L);
-}
-
-__device__ __forceinline__ f32x16 mfma3h(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl,
-                                         f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
-}
 
 // NSEG = 2: FVP ([RD_1 | D_1], with the E RH term); NSEG = 1: policy gradient (DS_1, no E term)
 // SW: segment 1 on one product from D_1's hi plane (decided per launch on the device, rbwd0_sw); the two
@@ -229,7 +193,7 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
       for (int i = 0; i < kR0XD; ++i) {
         const int kb = kR0XD * wv + i;   // wave-uniform: descriptor and LDS address in SGPRs
         const int pl = kb / (kR0XP / 2);
-        dma16(pl ? rXl : rXh, xsrc(kb) + (unsigned)t0 * 64u,
+        dma16(pl ? rXl : rXh, xsrc(kb) + (unsigned)t0 * 64u, 0u,
               lds_x + (unsigned)(pl * kR0XPL * 2 + (kb % (kR0XP / 2)) * 1024));
       }
     };
@@ -295,7 +259,7 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           unsigned short hh, ll;
-          split2h(st.ra[i][j] * sa, hh, ll);
+          split2_rn(st.ra[i][j] * sa, hh, ll);
           h[j] = hh;
           l[j] = ll;
         }
@@ -335,7 +299,7 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
           } else {
             const f16x8 al = *reinterpret_cast<const f16x8*>(As + kR0APL + ao);
 #pragma unroll
-            for (int tn = 0; tn < CT; ++tn) acc[tm][tn] = mfma3h(ah, al, bh[tn], bl[tn], acc[tm][tn]);
+            for (int tn = 0; tn < CT; ++tn) acc[tm][tn] = mfma3(ah, al, bh[tn], bl[tn], acc[tm][tn]);
           }
         }
       }
@@ -465,18 +429,17 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
             d[1][j] = d[2][j] = 0.25f;
             continue;
           }
-          d[0][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rH, vo, so, 0));
+          d[0][j] = ldbuf(rH, vo, so);
           if constexpr (kE) {
-            d[1][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rE, vo, so, 0));
+            d[1][j] = ldbuf(rE, vo, so);
             if constexpr (RP == 0) {
-              d[2][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rRH, vo, so, 0));
+              d[2][j] = ldbuf(rRH, vo, so);
             } else if ((j & 1) == 0) {
               // registers r, r + 1: rows 32 tm + (r & 3) + 8 (r >> 2) + 4 lh and the next, one pair
               const int sp = (16 * tm + ((r & 3) >> 1) + 4 * (r >> 2)) * kPairLd * 4;
-              d[2][j >> 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rPh, vp, sp, 0));
+              d[2][j >> 1] = ldbuf(rPh, vp, sp);
               if constexpr (RP == 2)
-                d[2][EC / 2 + (j >> 1)] =
-                    __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rPl, lo2 ? vp : kOob, sp, 0));
+                d[2][EC / 2 + (j >> 1)] = ldbuf(rPl, lo2 ? vp : kOob, sp);
             }
           } else {
             d[1][j] = 0.0f;
@@ -486,8 +449,7 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
       };
       // RH_1 of chunk register j from the planes' dwords: the f16 in the low (j even) or high half
       auto plane_rh = [&](const float (&d)[3][EC], int j) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        auto half = [&](float w) { return (float)__builtin_bit_cast(h2, w)[j & 1]; };
+        auto half = [&](float w) { return (float)__builtin_bit_cast(f16x2, w)[j & 1]; };
         float v = half(d[2][j >> 1]);
         if constexpr (RP == 2) v += half(d[2][EC / 2 + (j >> 1)]);
         return v * uR;
@@ -555,27 +517,27 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
           float vals[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) vals[j] = acc[s >> 1][tn][8 * (s & 1) + j];
-          split8h(vals, sR, bh[tn], bl[tn]);
+          split8(vals, sR, bh[tn], bl[tn]);
         }
 #pragma unroll
         for (int ot = 0; ot < kR0XT; ++ot) {
           f16x8 xa[2];
 #pragma unroll
           for (int pl = 0; pl < 2; ++pl) {
-            s8 v;
+            s16x8 v;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
               const int row = 16 * s + 8 * t + 4 * (g4 >> 1) + q;
               const int ch = 4 * ot + 2 * (g4 & 1) + (pp >> 1);
-              const s4 rr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                  (__attribute__((address_space(3))) s4*)(sX + pl * kR0XPL + (xoff(row, ch) >> 1) + 4 * (pp & 1)));
+              const s16x4 rr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                  (__attribute__((address_space(3))) s16x4*)(sX + pl * kR0XPL + (xoff(row, ch) >> 1) + 4 * (pp & 1)));
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[4 * t + e] = rr[e];
             }
             xa[pl] = __builtin_bit_cast(f16x8, v);
           }
 #pragma unroll
-          for (int tn = 0; tn < CT; ++tn) G[ot][tn] = mfma3h(xa[0], xa[1], bh[tn], bl[tn], G[ot][tn]);
+          for (int tn = 0; tn < CT; ++tn) G[ot][tn] = mfma3(xa[0], xa[1], bh[tn], bl[tn], G[ot][tn]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }

@@ -40,15 +40,12 @@
 // stepped down by exact powers of two when a later slice needs it: 0.65 ms slower at C4, the re-scaling branch
 // keeping 128 accumulator copies in VGPRs.)
 #include "chain_common.h"
-#include "rowepi.h"
 
 #include <stdexcept>
 #include <type_traits>
 
 namespace trpo {
 namespace {
-
-typedef __fp16 rf_h2 __attribute__((ext_vector_type(2)));
 
 #ifndef RF_SGB
 #define RF_SGB 1   // 1: each k-step region issues its next fragments' LDS reads before its MFMAs (sched_group_barrier)
@@ -78,30 +75,6 @@ constexpr int kRfChunks = 24;                  // chunks per tile
 constexpr int kRfLd = 256;                     // row stride of H1 / RH1 / RZ2 (floats; launch_rfwd01 checks)
 constexpr int kRfTile = 128, kRfWaves = 4;   // 4 waves of 32 states: 512 registers per wave
 
-// 8 values times s -> f16 hi and lo (round toward zero; x - hi is exact): fused16.hip split2 per pair
-__device__ __forceinline__ void rf_split8(const float* x, float s, f16x8& hi, f16x8& lo) {
-  cu32x4 H, L;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float a = x[2 * q] * s, b = x[2 * q + 1] * s;
-    const rf_h2 hp = __builtin_amdgcn_cvt_pkrtz(a, b);
-    const rf_h2 lp = __builtin_amdgcn_cvt_pkrtz(a - (float)hp[0], b - (float)hp[1]);
-    H[q] = __builtin_bit_cast(unsigned, hp);
-    L[q] = __builtin_bit_cast(unsigned, lp);
-  }
-  hi = __builtin_bit_cast(f16x8, H);
-  lo = __builtin_bit_cast(f16x8, L);
-}
-
-// c += a b on the split, smallest terms first
-__device__ __forceinline__ f32x16 rf_mfma3(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl,
-                                           f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
-  return c;
-}
-
 // ---- the chunk image (one per FVP: V0 and V1 change, W1 does not within an update) --------------------------
 // chunk 3t (A_t, 16 KB): [plane][feature f 0..31][unit u ^ (f & 15)] with unit u = 2 ks + h holding V0[obs 16 ks
 //   + 8 h + q][32 t + f], q = 0..7 (obs >= the real obs: 0);
@@ -118,7 +91,7 @@ __global__ void __launch_bounds__(256) rfwd01_img_kernel(const float* __restrict
   const int t = gid / 2560, rem = gid % 2560;
   if (t >= 8) return;
   float x[8];
-  cu32x4* dst;
+  u32x4* dst;
   int plane_units;
   float sc;
   if (rem < 512) {   // A_t: feature f, unit u
@@ -129,7 +102,7 @@ __global__ void __launch_bounds__(256) rfwd01_img_kernel(const float* __restrict
       x[q] = k < obs ? v[offV0 + (int64_t)k * 256 + 32 * t + f] : 0.0f;
     }
     sc = __builtin_ldexpf(1.0f, eV0);
-    dst = reinterpret_cast<cu32x4*>(img) + (size_t)(3 * t) * kRfUnits + f * 16 + (u ^ (f & 15));
+    dst = reinterpret_cast<u32x4*>(img) + (size_t)(3 * t) * kRfUnits + f * 16 + (u ^ (f & 15));
     plane_units = 512;
   } else {   // B_t,nh: matrix m, column r, unit u
     const int b = rem - 512, nh = b >> 10, m = (b >> 9) & 1, r = (b >> 2) & 127, u = b & 3, uu = u >> 1, h = u & 1;
@@ -140,20 +113,19 @@ __global__ void __launch_bounds__(256) rfwd01_img_kernel(const float* __restrict
       x[q] = src[offW1 + (int64_t)k * 256 + 128 * nh + r];
     }
     sc = __builtin_ldexpf(1.0f, m ? eV : eW);
-    dst = reinterpret_cast<cu32x4*>(img) + (size_t)(3 * t + 1 + nh) * kRfUnits + m * 1024 + r * 4 +
+    dst = reinterpret_cast<u32x4*>(img) + (size_t)(3 * t + 1 + nh) * kRfUnits + m * 1024 + r * 4 +
           (u ^ ((r >> 2) & 3));
     plane_units = 512;
   }
   f16x8 hi, lo;
-  rf_split8(x, sc, hi, lo);
-  dst[0] = __builtin_bit_cast(cu32x4, hi);
-  dst[plane_units] = __builtin_bit_cast(cu32x4, lo);
+  split8(x, sc, hi, lo);
+  dst[0] = __builtin_bit_cast(u32x4, hi);
+  dst[plane_units] = __builtin_bit_cast(u32x4, lo);
 }
 
-// One LDS-DMA instruction (buffer_load_dwordx4 ... lds): 16 B per lane from the buffer at voff + soff into LDS at the
-// wave-uniform byte address lds + 16 * lane (soff is added to the lane offset: an soffset operand must be an SGPR,
-// and a constant one would reach the assembler as a literal).  Inline asm, opaque to hipcc's s_waitcnt bookkeeping: the kernel counts
-// the completions itself (arrive()).  M0 is saved and restored around it (the compiler owns M0).
+// split.h's dma16 with soff folded into the lane offset and a literal 0 as the instruction's scalar offset: kept
+// local because dma16's SGPR operand would change this kernel's instructions.  The kernel counts the completions
+// itself (arrive()).
 __device__ __forceinline__ void rf_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, unsigned lds) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
@@ -170,7 +142,7 @@ __device__ __forceinline__ void rf_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned v
 // of one column and a lane holds one row, so lanes s, s ^ 1 exchange halves of a slice (one quad_perm DPP move per
 // value): the even lane then holds both rows of features 8 j + 4 h + i for j = 0, 1, the odd lane for j = 2, 3,
 // 4 consecutive dwords each: two 16-B stores per plane, the 4 store instructions per A chunk arrive() counts.
-// The split is rf_split8's (round toward zero, lo = the f16 of the exact remainder) at eR, not the A operand's
+// The split is split8's (round toward zero, lo = the f16 of the exact remainder) at eR, not the A operand's
 // per-state one: a K-along-rows reader cannot carry a per-row scale.  When n is odd the last pair's odd row (past
 // n: it would hold (1 - 0) c0) is zeroed after the tile loop by the workgroup that stored it.
 template <int KS0, bool PL>   // 16-deep k-steps over obs (obs <= 16 KS0)
@@ -179,7 +151,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
   // the ring: chunk c in slot c % 4.  An A chunk holds V0^T slice t (image units 0..1023) and H1 slice t of the
   // tile's 128 states (units 1024..2047, 256 per wave: row r, column unit cu at r * 8 + (cu ^ ((r >> 1) & 7)), so the
   // epilogue's reads of one column unit over 16 rows hit 16 distinct bank slots); a B chunk the W1 / V1 rows.
-  __shared__ cu32x4 q0[kRfUnits], q1[kRfUnits], q2[kRfUnits], q3[kRfUnits];
+  __shared__ u32x4 q0[kRfUnits], q1[kRfUnits], q2[kRfUnits], q3[kRfUnits];
   __shared__ float cvec[2][256];      // the tangent biases c0, c1
   __shared__ float red[3][16];
   __shared__ int pex[kRfWaves][32];   // per-state exponents, from the A-operand lanes to the accumulator lanes
@@ -232,7 +204,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
   const bool odd = (s & 1) != 0;
   const unsigned plane_lo = (unsigned)pair_plane_dwords(a.n);   // dwords (n < 2^23)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ordinary loads retired before the first DMA
-  auto slot = [&](int k) -> cu32x4* { return k == 0 ? q0 : k == 1 ? q1 : k == 2 ? q2 : q3; };
+  auto slot = [&](int k) -> u32x4* { return k == 0 ? q0 : k == 1 ? q1 : k == 2 ? q2 : q3; };
   auto rows_of = [&](int64_t r0w) { return (int)(a.n - r0w < 32 ? (a.n - r0w > 0 ? a.n - r0w : 0) : 32); };
   // chunk c (0..23) into slot sl (= c % 4), 8 DMA instructions per wave: a B chunk from the image; an A chunk half
   // from the image, half this wave's 32 H1 rows of slice t = c / 3 (r0w: the wave's first state of the chunk's tile;
@@ -284,7 +256,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
       for (int ks = 0; ks < KS0; ++ks) {
         unsigned u = (unsigned)row0 + ks;
         asm volatile("" : "+v"(u));
-        x[ks][0] = x[ks][1] = __builtin_bit_cast(f16x8, cu32x4{u, u, u, u});
+        x[ks][0] = x[ks][1] = __builtin_bit_cast(f16x8, u32x4{u, u, u, u});
       }
       return;
     }
@@ -353,7 +325,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
         const int cA3 = cA + 3 < kRfChunks ? cA + 3 : cA + 3 - kRfChunks;
         const int64_t rA3 = cA + 3 < kRfChunks ? r0 : r0n;
         if (!RF_ILV) dma(kA{}, cA3, (sA + 3) % 4, rA3);
-        const cu32x4* S = slot(sA);
+        const u32x4* S = slot(sA);
         float hv[16], cb[16];
         auto ldh = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -381,7 +353,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
           __builtin_amdgcn_sched_barrier(0);
           if (RF_ILV) dma_one(kA{}, cA3, (sA + 3) % 4, rA3, ks);
           if (ks + 1 < KS0) lda(ks + 1, fa[(ks + 1) & 1]);
-          if constexpr ((RF_ABL & 32) == 0) accA = rf_mfma3(fa[ks & 1][0], fa[ks & 1][1], xt[ks][0], xt[ks][1], accA);
+          if constexpr ((RF_ABL & 32) == 0) accA = mfma3(fa[ks & 1][0], fa[ks & 1][1], xt[ks][0], xt[ks][1], accA);
           if (RF_SGB && ks + 1 < KS0) {
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
@@ -414,16 +386,15 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
           // of columns at a time (the scheduling barrier keeps 8 packed dwords live, not 16)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            cu32x4 Hq, Lq;
+            u32x4 Hq, Lq;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const int i = 4 * j + q;
               const float nl = dpp_f<kDppX1>(rh[i]), nh = dpp_f<kDppX1>(rh[8 + i]);
               const float ev = (odd ? nh : rh[i]) * scR, od = (odd ? rh[8 + i] : nl) * scR;
-              const rf_h2 hp = __builtin_amdgcn_cvt_pkrtz(ev, od);
-              const rf_h2 lp = __builtin_amdgcn_cvt_pkrtz(ev - (float)hp[0], od - (float)hp[1]);
-              Hq[q] = __builtin_bit_cast(unsigned, hp);
-              Lq[q] = __builtin_bit_cast(unsigned, lp);
+              const u32x2 p = split2(ev, od);
+              Hq[q] = p[0];
+              Lq[q] = p[1];
             }
             if constexpr ((RF_ABL & 8) == 0) {
               __builtin_amdgcn_raw_buffer_store_b128(Hq, rph, hlane, (32 * t + 8 * j) * 4, 0);
@@ -435,7 +406,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
 #pragma unroll
           for (int j = 0; j < 4 && (RF_ABL & 8) == 0; ++j)
             __builtin_amdgcn_raw_buffer_store_b128(
-                __builtin_bit_cast(cu32x4, f32x4{rh[4 * j], rh[4 * j + 1], rh[4 * j + 2], rh[4 * j + 3]}), rrh, hlane,
+                __builtin_bit_cast(u32x4, f32x4{rh[4 * j], rh[4 * j + 1], rh[4 * j + 2], rh[4 * j + 3]}), rrh, hlane,
                 (32 * t + 8 * j) * 4, 0);
         }
         mR = fmaxf(mR, mt);
@@ -467,8 +438,8 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
         f16x8 aR[2][2], aH[2][2];   // k-step uu: registers 8 uu .. 8 uu + 7 (the permuted k order)
 #pragma unroll
         for (int uu = 0; uu < 2; ++uu) {
-          rf_split8(rh + 8 * uu, sR, aR[uu][0], aR[uu][1]);
-          rf_split8(hv + 8 * uu, sH, aH[uu][0], aH[uu][1]);
+          split8(rh + 8 * uu, sR, aR[uu][0], aR[uu][1]);
+          split8(hv + 8 * uu, sH, aH[uu][0], aH[uu][1]);
         }
         // ---- phase B: RZ2 += RH1_t W1_t + H1_t V1_t, output columns 128 nh .. 128 nh + 127 ----
 #pragma unroll
@@ -478,7 +449,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
           const int cB3 = cB + 3 < kRfChunks ? cB + 3 : cB + 3 - kRfChunks;
           const int64_t rB3 = cB + 3 < kRfChunks ? r0 : r0n;
           if (!RF_ILV) dma(kB{}, cB3, (sB + 3) % 4, rB3);
-          const cu32x4* B = slot(sB);
+          const u32x4* B = slot(sB);
           // step k = 4 uu + tn; its W / V fragments loaded one step ahead
           f16x8 fb[2][4];
           auto ldb = [&](int k, f16x8 (&f)[4]) __attribute__((always_inline)) {
@@ -499,8 +470,8 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) rfwd01_kernel(const Rfwd01Ar
             const f16x8(&f)[4] = fb[k & 1];
             if ((RF_ABL & 1) == 0) {
               f32x16 c = acc[4 * nh + tn];
-              c = rf_mfma3(aR[uu][0], aR[uu][1], f[0], f[1], c);
-              c = rf_mfma3(aH[uu][0], aH[uu][1], f[2], f[3], c);
+              c = mfma3(aR[uu][0], aR[uu][1], f[0], f[1], c);
+              c = mfma3(aH[uu][0], aH[uu][1], f[2], f[3], c);
               acc[4 * nh + tn] = c;
             }
             if (RF_SGB && (RF_ABL & 3) == 0 && k + 1 < 8) {
@@ -571,7 +542,7 @@ __global__ void __launch_bounds__(256) fwd01_img_kernel(const float* __restrict_
   const int t = gid / 1536, rem = gid % 1536;
   if (t >= 8) return;
   float x[8];
-  cu32x4* dst;
+  u32x4* dst;
   int plane_units;
   float sc;
   if (rem < 512) {   // A_t: feature f, unit u
@@ -582,7 +553,7 @@ __global__ void __launch_bounds__(256) fwd01_img_kernel(const float* __restrict_
       x[q] = k < obs ? th[offW0 + (int64_t)k * 256 + 32 * t + f] : 0.0f;
     }
     sc = __builtin_ldexpf(1.0f, eW0);
-    dst = reinterpret_cast<cu32x4*>(img) + (size_t)(2 * t) * kRfUnits + f * 16 + (u ^ (f & 15));
+    dst = reinterpret_cast<u32x4*>(img) + (size_t)(2 * t) * kRfUnits + f * 16 + (u ^ (f & 15));
     plane_units = 512;
   } else {   // B_t: column r, unit u
     const int b = rem - 512, r = b >> 2, u = b & 3, uu = u >> 1, h = u & 1;
@@ -592,18 +563,18 @@ __global__ void __launch_bounds__(256) fwd01_img_kernel(const float* __restrict_
       x[q] = th[offW1 + (int64_t)k * 256 + r];
     }
     sc = __builtin_ldexpf(1.0f, eW1);
-    dst = reinterpret_cast<cu32x4*>(img) + (size_t)(2 * t + 1) * kRfUnits + r * 4 + (u ^ ((r >> 2) & 3));
+    dst = reinterpret_cast<u32x4*>(img) + (size_t)(2 * t + 1) * kRfUnits + r * 4 + (u ^ ((r >> 2) & 3));
     plane_units = 1024;
   }
   f16x8 hi, lo;
-  rf_split8(x, sc, hi, lo);
-  dst[0] = __builtin_bit_cast(cu32x4, hi);
-  dst[plane_units] = __builtin_bit_cast(cu32x4, lo);
+  split8(x, sc, hi, lo);
+  dst[0] = __builtin_bit_cast(u32x4, hi);
+  dst[plane_units] = __builtin_bit_cast(u32x4, lo);
 }
 
 template <int KS0, bool PREP>
 __global__ void __launch_bounds__(kRfWaves * 64, 1) fwd01_kernel(const Fwd01Args a) {
-  __shared__ cu32x4 q0[kRfUnits], q1[kRfUnits], q2[kRfUnits], q3[kRfUnits];
+  __shared__ u32x4 q0[kRfUnits], q1[kRfUnits], q2[kRfUnits], q3[kRfUnits];
   __shared__ float cvec[2][256];      // the biases b0, b1
   const int tid = threadIdx.x, lane = tid & 63, s = lane & 31, h = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -623,7 +594,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) fwd01_kernel(const Fwd01Args
     cvec[1][i] = a.b1[i];
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ordinary loads retired before the first DMA
-  auto slot = [&](int k) -> cu32x4* { return k == 0 ? q0 : k == 1 ? q1 : k == 2 ? q2 : q3; };
+  auto slot = [&](int k) -> u32x4* { return k == 0 ? q0 : k == 1 ? q1 : k == 2 ? q2 : q3; };
   auto rows_of = [&](int64_t r0w) { return (int)(a.n - r0w < 32 ? (a.n - r0w > 0 ? a.n - r0w : 0) : 32); };
   // piece i of chunk c's DMA into slot sl: an A chunk has 4 pieces per wave (16 KB), a B chunk 8 (32 KB)
   auto dma_one = [&](int c, int sl, int i) __attribute__((always_inline)) {
@@ -683,7 +654,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) fwd01_kernel(const Fwd01Args
         // ---- phase A: Z0^T slice t; chunk cA + 3 (a B chunk) DMA'd one piece per k-step ----
         arrive(!first && t <= 1 ? 63 : (first && t == 0 ? 12 : 12 + S));
         const int cA3 = cA + 3 < kFwChunks ? cA + 3 : cA + 3 - kFwChunks;
-        const cu32x4* SA = slot(sA);
+        const u32x4* SA = slot(sA);
         f32x16 accA = f32x16{};
         f16x8 fa[2][2];
         auto lda = [&](int ks, f16x8 (&f)[2]) __attribute__((always_inline)) {
@@ -697,7 +668,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) fwd01_kernel(const Fwd01Args
           __builtin_amdgcn_sched_barrier(0);
           dma_one(cA3, (sA + 3) % 4, ks);
           if (ks + 1 < KS0) lda(ks + 1, fa[(ks + 1) & 1]);
-          accA = rf_mfma3(fa[ks & 1][0], fa[ks & 1][1], xt[ks][0], xt[ks][1], accA);
+          accA = mfma3(fa[ks & 1][0], fa[ks & 1][1], xt[ks][0], xt[ks][1], accA);
           if (RF_SGB && ks + 1 < KS0) {
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
@@ -715,16 +686,16 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) fwd01_kernel(const Fwd01Args
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             __builtin_amdgcn_raw_buffer_store_b128(
-                __builtin_bit_cast(cu32x4, f32x4{hv[4 * j], hv[4 * j + 1], hv[4 * j + 2], hv[4 * j + 3]}), rh1,
+                __builtin_bit_cast(u32x4, f32x4{hv[4 * j], hv[4 * j + 1], hv[4 * j + 2], hv[4 * j + 3]}), rh1,
                 hlane, (32 * t + 8 * j) * 4, 0);
         }
         f16x8 aH[2][2];
 #pragma unroll
-        for (int uu = 0; uu < 2; ++uu) rf_split8(hv + 8 * uu, sH, aH[uu][0], aH[uu][1]);
+        for (int uu = 0; uu < 2; ++uu) split8(hv + 8 * uu, sH, aH[uu][0], aH[uu][1]);
         // ---- phase B: Z1 += H1_t W1_t, all 256 columns; chunk cB + 3 (an A chunk) DMA'd over the first 4 steps ----
         arrive(!first && t == 0 ? 63 : (first && t == 0 ? 12 + S : 12 + 2 * S));
         const int cB3 = cB + 3 < kFwChunks ? cB + 3 : cB + 3 - kFwChunks;
-        const cu32x4* B = slot(sB);
+        const u32x4* B = slot(sB);
         f16x8 fb[2][2];
         auto ldb = [&](int k, f16x8 (&f)[2]) __attribute__((always_inline)) {   // k = 8 nh + 4 uu + tn
           const int col = 128 * (k >> 3) + 32 * (k & 3) + s;
@@ -739,7 +710,7 @@ __global__ void __launch_bounds__(kRfWaves * 64, 1) fwd01_kernel(const Fwd01Args
           if (k < 4) dma_one(cB3, (sB + 3) % 4, k);
           if (k + 1 < 16) ldb(k + 1, fb[(k + 1) & 1]);
           const int uu = (k >> 2) & 1, tn = k & 3, nh = k >> 3;
-          acc[4 * nh + tn] = rf_mfma3(aH[uu][0], aH[uu][1], fb[k & 1][0], fb[k & 1][1], acc[4 * nh + tn]);
+          acc[4 * nh + tn] = mfma3(aH[uu][0], aH[uu][1], fb[k & 1][0], fb[k & 1][1], acc[4 * nh + tn]);
           if (RF_SGB && k + 1 < 16) {
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);

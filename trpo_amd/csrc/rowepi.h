@@ -1,18 +1,10 @@
-// Device-side pieces shared by the row-GEMM translation units (gemm.hip, plane.hip): the fused
-// row epilogues, running-max bookkeeping, split helpers and the LDS-DMA primitive.  Everything is in an
-// anonymous namespace (internal linkage per translation unit).
+// The fused row epilogues of the row-GEMM kernels (gemm.hip, plane.hip, rbwd0.hip) and their running-max
+// bookkeeping.  Everything is in an anonymous namespace (internal linkage per translation unit).
 #pragma once
-#include "common.h"
-#include "kernels.h"
+#include "split.h"
 
 #ifndef TRPO_EPI_PIPE
 #define TRPO_EPI_PIPE 1    // 0: epilogue operand loads chunk by chunk (A/B builds only)
-#endif
-#ifndef TRPO_FAST_TANH
-#define TRPO_FAST_TANH 1   // 0: the device library's tanhf in the forward epilogues (A/B builds only)
-#endif
-#ifndef TRPO_HEAD_DPP
-#define TRPO_HEAD_DPP 1    // 0: head row reductions by ds_bpermute shuffles (A/B builds only)
 #endif
 #ifndef TRPO_EPI_TRACK
 #define TRPO_EPI_TRACK 1   // ablation builds only (tools): 0 drops the f16 running-max tracking
@@ -26,98 +18,6 @@
 
 namespace trpo {
 namespace {
-
-
-__device__ __forceinline__ float one_minus_sq(float h) { return (1.0f - h) * (1.0f + h); }
-
-// tanh for the forward epilogues (trpo_inksci.py:38 `tanh` layers), branch-free: both forms are
-// evaluated and one selected, where the device library's tanhf branches per lane (a wave runs both
-// sides under exec masks, ~35 VALU per element, which made the tanh epilogue ~2 ms of a 256-wide
-// C4 forward GEMM).  |x| < 0.625: x + x^3 P(x^2), the minimax odd polynomial of the device library's
-// own small-argument branch; otherwise (1 - t) / (1 + t) with t = 2^(-2|x| log2 e) from v_exp_f32
-// and v_rcp_f32 (a few ulp; t underflows to 0 past |x| ~ 44, giving 1).  Sign restored last.
-__device__ __forceinline__ float tanh_fast(float x) {
-#if TRPO_FAST_TANH
-  const float ax = fabsf(x);
-  const float x2 = x * x;
-  float p = __builtin_fmaf(-0.005700020585209131f, x2, 0.02063407190144062f);   // 0xbbbac73d, 0x3ca908c9
-  p = __builtin_fmaf(p, x2, -0.053737930953502655f);                        // 0xbd5c1c4e
-  p = __builtin_fmaf(p, x2, 0.13331416249275208f);                         // 0x3e088382
-  p = __builtin_fmaf(p, x2, -0.3333328068256378f);                        // 0xbeaaaa99
-  const float small = __builtin_fmaf(x2, ax * p, ax);
-  const float t = __builtin_amdgcn_exp2f(ax * -2.8853900817779268f);   // 2^(-2|x| log2 e) = e^(-2|x|)
-  const float r = __builtin_amdgcn_rcpf(1.0f + t);
-  const float big = __builtin_fmaf(-t, r, r);                          // (1 - t) / (1 + t)
-  return __builtin_copysignf(ax < 0.625f ? small : big, x);
-#else
-  return tanhf(x);
-#endif
-}
-
-#if TRPO_HEAD_DPP
-// 32-lane (wave-half) reductions on DPP moves + one ds_swizzle (common.h)
-__device__ __forceinline__ float hsum32(float v) { return sum32_dpp(v); }
-__device__ __forceinline__ double hsum32d(double v) { return sum32_dpp(v); }
-__device__ __forceinline__ float hmax32(float v) { return max32_dpp(v); }
-#else
-__device__ __forceinline__ float hsum32(float v) {
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 32);
-  return v;
-}
-__device__ __forceinline__ double hsum32d(double v) {
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 32);
-  return v;
-}
-__device__ __forceinline__ float hmax32(float v) {
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 32));
-  return v;
-}
-#endif
-__device__ __forceinline__ float hsum32t(float v) { return hsum32(v); }
-__device__ __forceinline__ double hsum32t(double v) { return hsum32d(v); }
-
-// workgroup max of v[i] >= 0 for the non-NULL slots, one atomicMax per slot per workgroup (float bits
-// order as unsigned for v >= 0) into the slot's counter for this block (kernels.h, kAmaxSub).
-// Every thread of the block must call it.
-// (`ext`, when given, is 48 floats of the caller's LDS to use instead of a static array: kernels whose
-// one LDS array already takes the whole 160 KB.)
-template <bool EXT = false>
-__device__ __forceinline__ void amax_commit3(unsigned* s0, float v0, unsigned* s1, float v1, unsigned* s2, float v2,
-                                             float (*ext)[16] = nullptr) {
-  if (!s0 && !s1 && !s2) return;
-  float(*red)[16];
-  if constexpr (EXT) {
-    red = ext;
-  } else {
-    __shared__ float red_own[3][16];
-    red = red_own;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    v0 = fmaxf(v0, __shfl_xor(v0, off, 64));
-    v1 = fmaxf(v1, __shfl_xor(v1, off, 64));
-    v2 = fmaxf(v2, __shfl_xor(v2, off, 64));
-  }
-  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[0][wave] = v0;
-    red[1][wave] = v1;
-    red[2][wave] = v2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    unsigned* slot = threadIdx.x == 0 ? s0 : (threadIdx.x == 1 ? s1 : s2);
-    if (slot) {
-      float m = 0.0f;
-      for (int w = 0; w < nw; ++w) m = fmaxf(m, red[threadIdx.x][w]);
-      const unsigned bid = blockIdx.x + blockIdx.y * 7919u + blockIdx.z * 104729u;
-      if (m > 0.0f) atomicMax(slot + (bid % kAmaxSub) * kAmaxStride, __float_as_uint(m));
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // element-wise epilogues (one accumulator element at (row, col))
@@ -224,14 +124,14 @@ __device__ __forceinline__ void epi_row(const RowEpiArgs& e, int row, bool rowva
       z[t] = real[t] ? v[t] + bias : -INFINITY;
       zm = fmaxf(zm, z[t]);
     }
-    const float m = hmax32(zm);
+    const float m = max32<TRPO_HEAD_DPP>(zm);
     float ex[TN], es = 0.0f;
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       ex[t] = real[t] ? expf(z[t] - m) : 0.0f;
       es += ex[t];
     }
-    const float ssum = hsum32(es);
+    const float ssum = sum32<TRPO_HEAD_DPP>(es);
     const int a = rowvalid ? av : 0;
     float p[TN], old[TN];
     float pa_l = 0.0f, olda_l = 0.0f;
@@ -256,8 +156,8 @@ __device__ __forceinline__ void epi_row(const RowEpiArgs& e, int row, bool rowva
       klp += real[t] ? od * log((od + (double)kEps) / (pd + (double)kEps)) : 0.0;
       enp += real[t] ? -pd * log(pd + (double)kEps) : 0.0;
     }
-    const double klt = hsum32d(klp);
-    const double ent = hsum32d(enp);
+    const double klt = sum32<TRPO_HEAD_DPP>(klp);
+    const double ent = sum32<TRPO_HEAD_DPP>(enp);
 #else
     // the reference's own precision (f32 tensors, trpo_inksci.py:50-51): f32 logs and f32 row sums of <= 32 TN
     // terms; the sums over rows are f64 (rowterms)
@@ -268,8 +168,8 @@ __device__ __forceinline__ void epi_row(const RowEpiArgs& e, int row, bool rowva
       klp += real[t] ? old[t] * lk : 0.0f;
       enp += real[t] ? -p[t] * le : 0.0f;
     }
-    const double klt = hsum32(klp);
-    const double ent = hsum32(enp);
+    const double klt = sum32<TRPO_HEAD_DPP>(klp);
+    const double ent = sum32<TRPO_HEAD_DPP>(enp);
 #endif
     const double sur = rowvalid ? (double)pa / (double)olda * (double)adv : 0.0;
     if (rowvalid && lr == 0) {
@@ -300,8 +200,8 @@ __device__ __forceinline__ void epi_row(const RowEpiArgs& e, int row, bool rowva
         spBp += pd * B[t];
         restp += (real[t] && 32 * t + lr != a) ? pd : T(0);
       }
-      const T spB = hsum32t(spBp);
-      const T rest = hsum32t(restp);   // 1 - p_a
+      const T spB = sum32<TRPO_HEAD_DPP>(spBp);
+      const T rest = sum32<TRPO_HEAD_DPP>(restp);   // 1 - p_a
       // surr logit delta (:54): -(adv/(N old_a)) p_a (1[j=a] - p_j)
       const T coef = -(T)adv * invN / (T)olda * (T)pa;
 #pragma unroll
@@ -334,7 +234,7 @@ __device__ __forceinline__ void epi_row(const RowEpiArgs& e, int row, bool rowva
       pd[t] = (rowvalid && real[t]) ? (double)pv : 0.0;
       przp += pd[t] * rz[t];
     }
-    const double prz = hsum32d(przp);
+    const double prz = sum32<TRPO_HEAD_DPP>(przp);
     double Rp[TN], Aa[TN], B[TN], spBp = 0.0, sRABp = 0.0;
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
@@ -345,8 +245,8 @@ __device__ __forceinline__ void epi_row(const RowEpiArgs& e, int row, bool rowva
       spBp += pd[t] * B[t];
       sRABp += Rp[t] * Aa[t] * B[t];
     }
-    const double spB = hsum32d(spBp);
-    const double sRAB = hsum32d(sRABp);
+    const double spB = sum32<TRPO_HEAD_DPP>(spBp);
+    const double sRAB = sum32<TRPO_HEAD_DPP>(sRABp);
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       const double rd = e.invN * (Rp[t] * (B[t] - spB) + Rp[t] * Aa[t] * Aa[t] + pd[t] * sRAB);
@@ -400,9 +300,6 @@ __device__ __forceinline__ void row_epi_full(const RowGemmArgs& args, f32x16 (&a
   const __amdgpu_buffer_rsrc_t rRH = mk(kRB ? e.RH : e.out0);
   const __amdgpu_buffer_rsrc_t rO1 = mk(kPB ? e.out1 : e.out0);
   const int vbase = ((wm * TM * 32 + 4 * lh) * ldo + n0 + wn * TN * 32 + lr) * 4;
-  auto ld = [&](__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
-  };
   auto st = [&](float v, __amdgpu_buffer_rsrc_t r, int vo, int so) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, vo, so, 0);
   };
@@ -420,10 +317,10 @@ __device__ __forceinline__ void row_epi_full(const RowGemmArgs& args, f32x16 (&a
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int so = (tm * 32 + (r & 3) + 8 * (r >> 2)) * ldo * 4;
-        dst[0][r] = ld(rH, vo, so);
+        dst[0][r] = ldbuf(rH, vo, so);
         if constexpr (NL == 3) {
-          dst[1][r] = ld(rE, vo, so);
-          dst[2][r] = ld(rRH, vo, so);
+          dst[1][r] = ldbuf(rE, vo, so);
+          dst[2][r] = ldbuf(rRH, vo, so);
         }
       }
     }
@@ -543,97 +440,6 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& args, f32x16 (&a
     }
   }
   amax_commit3<EXT_RED>(e.amax0, mx0, e.amax1, mx1, e.amax2, mx2, red);
-}
-
-// ---------------------------------------------------------------------------
-// Split-bf16 row GEMM.  CDNA4 has no reduced-precision f32 MFMA, but bf16 MFMA
-// runs at 16x the f32 rate.  Each f32 operand x is split exactly into three
-// bf16 pieces x = h + m + l + O(2^-27 |x|) (h = bf16(x), m = bf16(x - h),
-// l = bf16(x - h - m); both differences are exact in f32) and
-//     a*b ~= ah bh + (ah bm + am bh) + (ah bl + al bh + am bm)
-// keeps every product term down to 2^-18 relative; the dropped ones (am bl,
-// al bm, al bl) are < 2^-26 relative, below the f32 rounding of the sum.  The
-// pieces' products are exact in the MFMA's f32 accumulation, so the result
-// matches an f32 GEMM to f32 rounding at 16/6 = 2.7x its MFMA peak.
-//
-// A (activations, f32 in HBM) is split while staging global -> LDS; B (packed
-// weights) is pre-split by split_b_kernel into [3][Npad][ldk] planes.
-// v_mfma_f32_32x32x16_bf16: lane l (r = l&31, h = l>>5) holds A[r][8h..8h+7]
-// and B[8h..8h+7][col r] - one ds_read_b128 per plane from [row][k] images.
-// ---------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned short bf16_bits(float x) {
-  return __builtin_bit_cast(unsigned short, (__bf16)x);
-}
-__device__ __forceinline__ float bf16_val(unsigned short b) {
-  return __builtin_bit_cast(float, (unsigned)b << 16);
-}
-__device__ __forceinline__ void split3(float x, unsigned short& h, unsigned short& m, unsigned short& l) {
-  h = bf16_bits(x);
-  const float r1 = x - bf16_val(h);
-  m = bf16_bits(r1);
-  const float r2 = r1 - bf16_val(m);
-  l = bf16_bits(r2);
-}
-
-// f16 split (RowGemmArgs::f16): x (already scaled into [2^11, 2^12) by a power of two, see
-// f16_scale_exp) = h + l + O(2^-22 |x|) with h = f16(x), l = f16(x - h) (the difference is exact);
-// a*b ~= ah bh + (ah bl + al bh), the dropped al bl is ~2^-22 relative.  f16 MFMA runs at the bf16
-// rate, so 3 products instead of 6 halve the MFMA work; the scales keep every piece a normal f16
-// down to 2^-15 of the operand's max (below that the error is absolute, 2^-36 of the max).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split2h(float x, unsigned short& h, unsigned short& l) {
-  const _Float16 hh = (_Float16)x;
-  const _Float16 ll = (_Float16)(x - (float)hh);
-  h = __builtin_bit_cast(unsigned short, hh);
-  l = __builtin_bit_cast(unsigned short, ll);
-}
-// the slot's max (over its kAmaxSub counters, kAmaxSub / 64 per lane) -> scale exponent; all lanes of
-// the wave must call it
-__device__ __forceinline__ int amax_exp(const unsigned* amax) {
-  if (!amax) return f16_scale_exp(1.0f);
-  const int lane = threadIdx.x & 63;
-  float v = 0.0f;
-#pragma unroll
-  for (int i = 0; i < kAmaxSub / 64; ++i) v = fmaxf(v, __uint_as_float(amax[(lane + 64 * i) * kAmaxStride]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return f16_scale_exp(v);
-}
-template <int TM, int TN>
-__device__ __forceinline__ void scale_acc(f32x16 (&acc)[TM][TN], int e) {
-  if (e == 0) return;
-  const float f = __builtin_ldexpf(1.0f, e);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] *= f;
-}
-
-// LDS images are [row][16 k] bf16 (32-B rows, no padding); the two 16-B k-chunks of
-// a row swap places where bit 2 ^ bit 3 of the row is set.
-// (The flip bit is bit 2 ^ bit 3 of the row: the ds_read_b128 fragment reads, serviced in the lane groups
-// {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32), put their 16 rows on 16 distinct 16-B bank slots, and so do the
-// weight-gradient staging stores -- ds_write_b128, 8 lanes per LDS cycle on 32 banks, 8 consecutive rows of one
-// chunk -- which a bit-3-only flip left 2-way conflicted, rows r and r+4 on the same banks.)
-__device__ __forceinline__ int swz16(int row, int chunk) {
-  return row * 16 + ((chunk ^ (((row >> 2) ^ (row >> 3)) & 1)) << 3);
-}
-
-// One global_load_lds_dwordx4 as inline asm: 16 B per lane from `src` into LDS at the wave-uniform
-// byte address `lds` + 16 * lane.  Opaque to hipcc's s_waitcnt bookkeeping (the builtin form makes
-// hipcc drain vmcnt(0) before every later LDS read), so the caller counts completion itself.
-__device__ __forceinline__ void glds16(const void* src, const void* lds) {
-  unsigned keep;
-  const unsigned dst = (unsigned)(uintptr_t)lds;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(__builtin_amdgcn_readfirstlane(dst))
-               : "memory");
 }
 
 }  // namespace

@@ -164,29 +164,9 @@ int trpo_gae(const double* rewards, const double* values, const uint8_t* starts,
   });
 }
 
-static int* option_slot(const std::string& k) {
-  if (k == "split_mfma") return &g_options.split_mfma;
-  if (k == "split_wg") return &g_options.split_wg;
-  if (k == "chain") return &g_options.chain;
-  if (k == "split_f16") return &g_options.split_f16;
-  if (k == "split_min_k") return &g_options.split_min_k;
-  if (k == "graphs") return &g_options.graphs;
-  if (k == "tail") return &g_options.tail;
-  if (k == "fused") return &g_options.fused;
-  if (k == "low_seg") return &g_options.low_seg;
-  if (k == "planes") return &g_options.planes;
-  if (k == "rbwd0") return &g_options.rbwd0;
-  if (k == "hbwd2") return &g_options.hbwd2;
-  if (k == "head_fwd") return &g_options.head_fwd;
-  if (k == "splits") return &g_options.splits;
-  if (k == "pg_splits") return &g_options.pg_splits;
-  if (k == "ls_fused") return &g_options.ls_fused;
-  if (k == "cg_fuse_reduce") return &g_options.cg_fuse_reduce;
-  if (k == "rfwd01") return &g_options.rfwd01;
-  if (k == "fwd01") return &g_options.fwd01;
-  if (k == "rh1_planes") return &g_options.rh1_planes;
-  if (k == "cg_p_img") return &g_options.cg_p_img;
-  throw ArgError("unknown option " + k);
+static int* known_option(const char* name) {
+  if (int* slot = option_slot(name)) return slot;
+  throw ArgError(std::string("unknown option ") + name);
 }
 
 int trpo_plane_rows_ok(int64_t x_mpad, int* rfwd01_ok, int* pair_planes_ok) {
@@ -200,14 +180,14 @@ int trpo_plane_rows_ok(int64_t x_mpad, int* rfwd01_ok, int* pair_planes_ok) {
 int trpo_set_option(const char* name, int value) {
   return guarded([&] {
     REQUIRE(name, "NULL argument");
-    *option_slot(name) = value;
+    *known_option(name) = value;
   });
 }
 
 int trpo_get_option(const char* name, int* value) {
   return guarded([&] {
     REQUIRE(name && value, "NULL argument");
-    *value = *option_slot(name);
+    *value = *known_option(name);
   });
 }
 

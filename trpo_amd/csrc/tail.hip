@@ -12,7 +12,7 @@
 // are read once from HBM, E = -2 DH H is recomputed from D_L (K = b), and only RD_{L-2} is written.
 //
 // Arithmetic: every product on v_mfma_f32_32x32x16_f16 with each fp32 operand scaled by a power of
-// two and split into f16 hi + lo (3 products, 2^-22 relative; gemm.hip rowgemm3_kernel).  Scales:
+// two and split into f16 hi + lo (3 products; split.h).  Scales:
 // RH / D_L / W / V from the engine's running-max slots, H fixed (|tanh| <= 1), RD_L per tile
 // (it is produced here).  Every accumulator is unscaled to true f32 values before it is combined.
 //
@@ -26,83 +26,20 @@
 //     and in C layout (G products).
 // Block = 8 waves (two per SIMD), wave w owns hidden columns [32w, 32w + 32); one block per
 // split-K slab.
-#include "common.h"
-#include "kernels.h"
+#include "split.h"
 
 #include <stdexcept>
 
 namespace trpo {
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int TR = 32;       // rows per tile
 constexpr int NW = 8;        // waves per block; wave w owns hidden columns [32w, 32w + 32)
 constexpr int SLD = 36;      // row stride (floats) of the [row][action] LDS tiles
 
-__device__ __forceinline__ float omsq(float h) { return (1.0f - h) * (1.0f + h); }
-
-#ifndef TRPO_TAIL_DPP
-#define TRPO_TAIL_DPP 1    // 0: R-softmax row sums by ds_bpermute shuffles (A/B builds only)
-#endif
-template <class T>
-__device__ __forceinline__ T hsum32t(T v) {
-#if TRPO_TAIL_DPP
-  return sum32_dpp(v);   // common.h: DPP moves + one ds_swizzle
-#else
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 32);
-  return v;
-#endif
-}
 #ifndef TRPO_TAIL_HEAD64
 #define TRPO_TAIL_HEAD64 0
 #endif
-
-// the max of a running-max slot (kAmaxSub counters) -> power-of-two scale exponent; whole wave
-__device__ __forceinline__ int slot_exp(const unsigned* amax) {
-  if (!amax) return f16_scale_exp(1.0f);
-  const int lane = threadIdx.x & 63;
-  float v = 0.0f;
-#pragma unroll
-  for (int i = 0; i < kAmaxSub / 64; ++i) v = fmaxf(v, __uint_as_float(amax[(lane + 64 * i) * kAmaxStride]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return f16_scale_exp(v);
-}
-
-// x * 2^e -> f16 hi + lo, two elements per packed conversion (v_cvt_pkrtz_f16_f32).  Round toward
-// zero: x - hi is exact in f32 and |x - hi| < ulp16(x), so lo keeps hi + lo within 2^-21 |x|.
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split8(const float* x, float s, h8& hi, h8& lo) {
-  u32x4 H, L;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i] * s, b = x[2 * i + 1] * s;
-    const fp16x2 hp = __builtin_amdgcn_cvt_pkrtz(a, b);
-    const fp16x2 lp = __builtin_amdgcn_cvt_pkrtz(a - (float)hp[0], b - (float)hp[1]);
-    H[i] = __builtin_bit_cast(unsigned, hp);
-    L[i] = __builtin_bit_cast(unsigned, lp);
-  }
-  hi = __builtin_bit_cast(h8, H);
-  lo = __builtin_bit_cast(h8, L);
-}
-
-
-
-// a*b ~= ah bh + ah bl + al bh, smallest terms first
-__device__ __forceinline__ f32x16 mfma3(const h8& ah, const h8& al, const h8& bh, const h8& bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
-  return c;
-}
-
-__device__ __forceinline__ float ldb(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
-}
 
 // head planes in LDS: [mat][plane][j][k] u16, the 16-B chunk c of row j stored at c ^ (j & 15)
 __device__ __forceinline__ int sw_off(int mat, int plane, int j, int k) {
@@ -132,7 +69,7 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
   const int col0 = 32 * w;                    // this wave's hidden columns [col0, col0 + 32)
   const bool wv = col0 < apad;
 
-  const int eRH = slot_exp(A.am_rh), eD = slot_exp(A.am_d), eW = slot_exp(A.am_w), eV = slot_exp(A.am_v);
+  const int eRH = amax_exp(A.am_rh), eD = amax_exp(A.am_d), eW = amax_exp(A.am_w), eV = amax_exp(A.am_v);
   const int eH = f16_scale_exp(1.0f);
   const float sRHf = __builtin_ldexpf(1.0f, eRH), sDf = __builtin_ldexpf(1.0f, eD), sHf = __builtin_ldexpf(1.0f, eH);
 
@@ -145,7 +82,7 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
   }
 
   // ---- R-backward B fragments (constant): [W^T ; V^T] planes [n][k], n = col0 + lr, k = 16s + 8lh ----
-  h8 wt[2][2], vt[2][2];   // [s][plane]
+  f16x8 wt[2][2], vt[2][2];   // [s][plane]
   {
     const int n = col0 + lr;
     const bool nv = n < apad;
@@ -156,8 +93,8 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
         const size_t o = (size_t)p * A.bplane + (size_t)(nv ? n : 0) * 32 + 16 * s + 8 * lh;
         const u16x8 x = *reinterpret_cast<const u16x8*>(A.WT16 + o);
         const u16x8 y = *reinterpret_cast<const u16x8*>(A.VT16 + o);
-        wt[s][p] = nv ? __builtin_bit_cast(h8, x) : h8{};
-        vt[s][p] = nv ? __builtin_bit_cast(h8, y) : h8{};
+        wt[s][p] = nv ? __builtin_bit_cast(f16x8, x) : f16x8{};
+        vt[s][p] = nv ? __builtin_bit_cast(f16x8, y) : f16x8{};
       }
   }
   __syncthreads();
@@ -180,14 +117,14 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int so = ((i & 3) + 8 * (i >> 2)) * apad * 4;
-      rh[i] = ldb(rRH, vo_c, so);
-      h[i] = ldb(rH, vo_c, so);
+      rh[i] = ldbuf(rRH, vo_c, so);
+      h[i] = ldbuf(rH, vo_c, so);
     }
     const __amdgpu_buffer_rsrc_t rP = desc(A.P, t0, bpad), rDL = desc(A.DL, t0, bpad);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      pp[q] = ldb(rP, vo_h, q * bpad * 4);
-      dd[q] = ldb(rDL, vo_h, q * bpad * 4);
+      pp[q] = ldbuf(rP, vo_h, q * bpad * 4);
+      dd[q] = ldbuf(rDL, vo_h, q * bpad * 4);
     }
   };
 
@@ -201,7 +138,7 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
     // (RowEpi::kRZ); the same f32 operations as its kRHidden epilogue, so R{h} is bit-identical
     if (A.rz) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) cRH[i] = omsq(cH[i]) * cRH[i];
+      for (int i = 0; i < 16; ++i) cRH[i] = one_minus_sq(cH[i]) * cRH[i];
     }
 
     // ---- head R-forward partial over this wave's 32 columns: RZ = RH W + H V.  The tile's C layout
@@ -215,46 +152,43 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
     };
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
-      h8 hi, lo;
+      f16x8 hi, lo;
 #pragma unroll
       for (int mat = 0; mat < 2; ++mat) {
         split8(mat == 0 ? &cRH[8 * s2] : &cH[8 * s2], mat == 0 ? sRHf : sHf, hi, lo);
-        typedef short s4 __attribute__((ext_vector_type(4)));
-        const s4* hp = reinterpret_cast<const s4*>(&hi);
-        const s4* lp = reinterpret_cast<const s4*>(&lo);
+        const s16x4* hp = reinterpret_cast<const s16x4*>(&hi);
+        const s16x4* lp = reinterpret_cast<const s16x4*>(&lo);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
           const int m = 16 * s2 + 8 * half + 4 * lh;
-          *reinterpret_cast<s4*>(xw + xoff(mat, 0, lr, m)) = hp[half];
-          *reinterpret_cast<s4*>(xw + xoff(mat, 1, lr, m)) = lp[half];
+          *reinterpret_cast<s16x4*>(xw + xoff(mat, 0, lr, m)) = hp[half];
+          *reinterpret_cast<s16x4*>(xw + xoff(mat, 1, lr, m)) = lp[half];
         }
       }
     }
     {
-      typedef short s4 __attribute__((ext_vector_type(4)));
-      typedef short s8 __attribute__((ext_vector_type(8)));
       const int g4 = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
       const int mrow = 16 * (g4 & 1) + 4 * pp;             // the 4 columns (rows m) this lane addresses
       f32x16 acc = f32x16{}, accv = f32x16{};
       auto tr8 = [&](int mat, int pl, int s2) {
-        s8 v;
+        s16x8 v;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int k = 16 * s2 + 8 * (g4 >> 1) + 4 * t + q;
-          const s4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) s4*)(xw + xoff(mat, pl, k, mrow)));
+          const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) s16x4*)(xw + xoff(mat, pl, k, mrow)));
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[4 * t + e] = r[e];
         }
-        return __builtin_bit_cast(h8, v);
+        return __builtin_bit_cast(f16x8, v);
       };
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const int k = col0 + 16 * s2 + 8 * lh;
-        acc = mfma3(tr8(0, 0, s2), tr8(0, 1, s2), *reinterpret_cast<const h8*>(sW + sw_off(0, 0, lr, k)),
-                    *reinterpret_cast<const h8*>(sW + sw_off(0, 1, lr, k)), acc);
-        accv = mfma3(tr8(1, 0, s2), tr8(1, 1, s2), *reinterpret_cast<const h8*>(sW + sw_off(1, 0, lr, k)),
-                     *reinterpret_cast<const h8*>(sW + sw_off(1, 1, lr, k)), accv);
+        acc = mfma3(tr8(0, 0, s2), tr8(0, 1, s2), *reinterpret_cast<const f16x8*>(sW + sw_off(0, 0, lr, k)),
+                    *reinterpret_cast<const f16x8*>(sW + sw_off(0, 1, lr, k)), acc);
+        accv = mfma3(tr8(1, 0, s2), tr8(1, 1, s2), *reinterpret_cast<const f16x8*>(sW + sw_off(1, 0, lr, k)),
+                     *reinterpret_cast<const f16x8*>(sW + sw_off(1, 1, lr, k)), accv);
       }
       const float f0 = __builtin_ldexpf(1.0f, -(eRH + eW)), f1 = __builtin_ldexpf(1.0f, -(eH + eV));
       float* rzw = reinterpret_cast<float*>(xw);            // the planes are consumed: reuse the bytes
@@ -285,13 +219,13 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
 #endif
         const T rz = real ? (T)z : T(0);
         const T pd = real ? (T)cP[q] : T(0);    // rows past the split: P = 0 -> RD = 0
-        const T prz = hsum32t(pd * rz);
+        const T prz = sum32<TRPO_TAIL_DPP>(pd * rz);
         const T Rp = pd * (rz - prz);
         const T inv = T(1) / (pd + (T)kEps);
         const T Aa = real ? pd * inv : T(0);
         const T B = real ? (T)kEps * inv : T(0);
-        const T spB = hsum32t(pd * B);
-        const T sRAB = hsum32t(Rp * Aa * B);
+        const T spB = sum32<TRPO_TAIL_DPP>(pd * B);
+        const T sRAB = sum32<TRPO_TAIL_DPP>(Rp * Aa * B);
         const T rd = (T)A.invN * (Rp * (B - spB) + Rp * Aa * Aa + pd * sRAB);
         const float rdf = real ? (float)rd : 0.0f;
         const int row = hrow0 + q;
@@ -313,7 +247,6 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
 
     // ---- [RD_L ; D_L] -> f16 planes, rows 4w..4w+3 by wave w; the 16-B chunk c of row r sits at
     //      c ^ ((r >> 2) & 3) (conflict-free A-fragment reads; tr16 reads of 4 consecutive rows) ----
-    typedef short s4 __attribute__((ext_vector_type(4)));
     auto pof = [](int mat, int pl, int row, int col) {
       return ((mat * 2 + pl) * TR + row) * 32 + ((((col >> 3) ^ ((row >> 2) & 3))) << 3) + (col & 7);
     };
@@ -324,10 +257,9 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
         const float sc = mat == 0 ? sRDf : sDf;
         const float a = (mat == 0 ? sRD[par][row][col] : sD[par][row][col]) * sc;
         const float bb = (mat == 0 ? sRD[par][row][col + 1] : sD[par][row][col + 1]) * sc;
-        const fp16x2 hp = __builtin_amdgcn_cvt_pkrtz(a, bb);
-        const fp16x2 lp = __builtin_amdgcn_cvt_pkrtz(a - (float)hp[0], bb - (float)hp[1]);
-        *reinterpret_cast<fp16x2*>(sP + pof(mat, 0, row, col)) = hp;
-        *reinterpret_cast<fp16x2*>(sP + pof(mat, 1, row, col)) = lp;
+        const u32x2 p = split2(a, bb);
+        *reinterpret_cast<unsigned*>(sP + pof(mat, 0, row, col)) = p[0];
+        *reinterpret_cast<unsigned*>(sP + pof(mat, 1, row, col)) = p[1];
       }
     }
     lds_barrier();
@@ -338,10 +270,10 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int col = 16 * s + 8 * lh;
-      const h8 rh_ = *reinterpret_cast<const h8*>(sP + pof(0, 0, lr, col));
-      const h8 rl_ = *reinterpret_cast<const h8*>(sP + pof(0, 1, lr, col));
-      const h8 dh_ = *reinterpret_cast<const h8*>(sP + pof(1, 0, lr, col));
-      const h8 dl_ = *reinterpret_cast<const h8*>(sP + pof(1, 1, lr, col));
+      const f16x8 rh_ = *reinterpret_cast<const f16x8*>(sP + pof(0, 0, lr, col));
+      const f16x8 rl_ = *reinterpret_cast<const f16x8*>(sP + pof(0, 1, lr, col));
+      const f16x8 dh_ = *reinterpret_cast<const f16x8*>(sP + pof(1, 0, lr, col));
+      const f16x8 dl_ = *reinterpret_cast<const f16x8*>(sP + pof(1, 1, lr, col));
       aRW = mfma3(rh_, rl_, wt[s][0], wt[s][1], aRW);
       aDV = mfma3(dh_, dl_, vt[s][0], vt[s][1], aDV);
       aDW = mfma3(dh_, dl_, wt[s][0], wt[s][1], aDW);
@@ -357,7 +289,7 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
         const float dh = aDW[i] * fDW;
         const float h = cH[i], rh = cRH[i];
         const float e = -2.0f * dh * h;
-        const float o = fmaf(e, rh, rdh * omsq(h));
+        const float o = fmaf(e, rh, rdh * one_minus_sq(h));
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), rOut, vo_c,
                                               ((i & 3) + 8 * (i >> 2)) * apad * 4, 0);
         mxo = fmaxf(mxo, fabsf(o));
@@ -367,24 +299,23 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
     //      action, element e of k-step s = row 16s + 8(e>>2) + 4lh + (e&3)) by transposed reads of
     //      the planes: lane 4q+p of a 16-lane group addresses row r0 + q, actions 4p .. 4p+3 ----
     {
-      typedef short s8 __attribute__((ext_vector_type(8)));
       const int g4 = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
       auto trb = [&](int mat, int pl, int s2) {
-        s8 v;
+        s16x8 v;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int row = 16 * s2 + 4 * (g4 >> 1) + 8 * t + q;
-          const s4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) s4*)(sP + pof(mat, pl, row, 16 * (g4 & 1) + 4 * pp)));
+          const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) s16x4*)(sP + pof(mat, pl, row, 16 * (g4 & 1) + 4 * pp)));
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[4 * t + e] = r[e];
         }
-        return __builtin_bit_cast(h8, v);
+        return __builtin_bit_cast(f16x8, v);
       };
       f32x16 g0 = f32x16{}, g1 = f32x16{};
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        h8 ah, al;
+        f16x8 ah, al;
         split8(&cRH[8 * s], sRHf, ah, al);
         g0 = mfma3(ah, al, trb(1, 0, s), trb(1, 1, s), g0);
         split8(&cH[8 * s], sHf, ah, al);
@@ -441,16 +372,16 @@ __global__ void __launch_bounds__(NW * 64, 1) fvp_tail_kernel(const TailArgs A) 
 __global__ void __launch_bounds__(256) tail_pack_kernel(const TailPackArgs P) {
   const int mat = blockIdx.y;
   const float* src = (mat == 0 ? P.theta : P.v) + P.off_w;
-  const int e = slot_exp(mat == 0 ? P.am_w : P.am_v);   // whole wave, before any exit
+  const int e = amax_exp(mat == 0 ? P.am_w : P.am_v);   // whole wave, before any exit
   const float s = __builtin_ldexpf(1.0f, e);
   const int idx = blockIdx.x * 256 + threadIdx.x;       // over 32 j x kTailK k
   if (idx >= 32 * kTailK) return;
   const int j = idx / kTailK, k = idx % kTailK;
   const float x = (j < P.b && k < P.a) ? src[(size_t)k * P.b + j] * s : 0.0f;
-  const _Float16 hh = (_Float16)x;
-  const _Float16 ll = (_Float16)(x - (float)hh);
-  P.out[((size_t)(mat * 2 + 0) * 32 + j) * kTailK + k] = __builtin_bit_cast(unsigned short, hh);
-  P.out[((size_t)(mat * 2 + 1) * 32 + j) * kTailK + k] = __builtin_bit_cast(unsigned short, ll);
+  unsigned short hh, ll;
+  split2_rn(x, hh, ll);
+  P.out[((size_t)(mat * 2 + 0) * 32 + j) * kTailK + k] = hh;
+  P.out[((size_t)(mat * 2 + 1) * 32 + j) * kTailK + k] = ll;
 }
 
 }  // namespace

@@ -130,8 +130,6 @@ constexpr int kCgStepMax = kRedBlocks * kRsCols;        // P limit: the fixed pa
 constexpr int kCgStepPer = kCgStepMax / (kRsCols * kRsGroups);   // parameters per thread of the last block (16)
 static_assert(kRsCols * kRsGroups == 1024 && kRedThreads == 256, "cg_step: 16 waves replay 4-wave blocks");
 
-typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
-
 __global__ void __launch_bounds__(kRsCols* kRsGroups)
 cg_step_slabs_kernel(const CgStepArgs a, const ChainImgArgs img, int* img_e) {
   __shared__ float red[kRsGroups][kRsCols + 1];
@@ -306,18 +304,16 @@ cg_step_slabs_kernel(const CgStepArgs a, const ChainImgArgs img, int* img_e) {
         const bool in = o < jb.O && k < jb.K;
         x[q] = in ? src[jb.trans ? o * jb.ldw + k : k * jb.ldw + o] * sc : 0.0f;
       }
-      cu32x4 H, L;
+      u32x4 H, L;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {   // fused16.hip split2.  (Routing hi through the cu32x4 and back by bit_cast
-        // made hipcc subtract pair 0's hi from every pair: kept in fp16x2 registers here)
-        const fp16x2_t hp = __builtin_amdgcn_cvt_pkrtz(x[2 * q], x[2 * q + 1]);
-        const fp16x2_t lp = __builtin_amdgcn_cvt_pkrtz(x[2 * q] - (float)hp[0], x[2 * q + 1] - (float)hp[1]);
-        H[q] = __builtin_bit_cast(unsigned, hp);
-        L[q] = __builtin_bit_cast(unsigned, lp);
+      for (int q = 0; q < 4; ++q) {
+        const u32x2 p = split2(x[2 * q], x[2 * q + 1]);
+        H[q] = p[0];
+        L[q] = p[1];
       }
       unsigned short* dst = img.img + jb.dst_off + (size_t)c * 2 * jb.otp * 32 + o * 32 + ((gg ^ chain_hsw(o)) << 3);
-      *reinterpret_cast<cu32x4*>(dst) = H;
-      *reinterpret_cast<cu32x4*>(dst + (size_t)jb.otp * 32) = L;
+      *reinterpret_cast<u32x4*>(dst) = H;
+      *reinterpret_cast<u32x4*>(dst + (size_t)jb.otp * 32) = L;
     }
   }
 }
