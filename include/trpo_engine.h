@@ -81,6 +81,52 @@ typedef struct trpo_update_stats {
  * no bound; a softmax row spans up to 4 x 32 lanes here). */
 int trpo_create(trpo_engine** out, int obs_dim, const int* hidden, int n_hidden, int n_actions,
                 int64_t max_rows, int device);
+
+/* ---- the policy's distribution family -----------------------------------------------------
+ * TRPO_DIST_CATEGORICAL is the reference's softmax policy (trpo_create).  TRPO_DIST_GAUSSIAN is the
+ * diagonal-Gaussian policy of continuous control, which the reference does not have: the equations
+ * below are its definition.
+ *
+ * Policy.  The same tanh-MLP; its last layer is linear and gives the mean mu(s) in R^A.  The parameters
+ * gain a state-independent log-std vector s in R^A, sigma = exp(s), stored last in the flat layout:
+ * [W1, b1, ..., WL, bL, logstd], so P = sum(fan_in*fan_out + fan_out) + A, and every P-long vector
+ * (theta, g, v, Hv, stepdir, fullstep) carries that tail.
+ *
+ * Feed.  states [n][obs] f32, actions [n][A] f32, advant [n] f32, old_mean [n][A] f32 (mu0) and
+ * old_logstd [A] f32 (s0).  With z = (a - mu)/sigma and z0 = (a - mu0)/sigma0 per dimension d and
+ * N = n_global:
+ *   log r_n = sum_d [(s0_d - s_d) + (z0_d^2 - z_d^2)/2]
+ *   surr    = -(1/N) sum_n adv_n exp(log r_n)
+ *   kl      = (1/N) sum_n sum_d [s_d - s0_d + (sigma0_d^2 + (mu0_nd - mu_nd)^2)/(2 sigma_d^2) - 1/2]   (KL(old || new))
+ *   ent     = (1/N) sum_n sum_d [s_d + ln(2 pi e)/2]
+ * The mean is float32; the per-row log-ratio, KL and entropy terms are formed from it in float64 (the KL and
+ * the log-ratio are differences of near-equal terms) and summed over rows in float64.
+ *
+ * Policy gradient.  g = grad_theta surr: the head delta DS_L[n,d] = -(adv_n r_n / N) z_nd / sigma_d followed by
+ * the usual backprop, and on the tail g_s[d] = -(1/N) sum_n adv_n r_n (z_nd^2 - 1).
+ *
+ * FVP.  Hv is the Hessian-vector product of KL_ff(theta) = kl with (mu0, s0) := stop_grad(mu(theta), s) at the
+ * same theta (the construction of trpo_inksci.py:56-70).  In closed form: the R-forward R{mu} = J_mu v;
+ * RD_L = R{mu} / (sigma^2 N); backprop of RD_L like a policy gradient (at theta = theta_old the plain KL
+ * backward is exactly zero, so no other term survives); Hv_s = 2 v_s (n/N) on the tail, each rank's partial,
+ * which sums to 2 v_s over ranks.
+ *
+ * Sampling.  a = mu + sigma xi with xi [n][A] f64 standard normals given by the caller, evaluated in float64
+ * and rounded to float32; train = 0 gives a = mu.
+ *
+ * On a Gaussian engine trpo_losses, trpo_eval_losses, trpo_policy_grad, trpo_fvp, trpo_cg, trpo_linesearch,
+ * trpo_update, trpo_get/set_flat, trpo_get_vector, trpo_set_rewards, trpo_compute_advantages, the
+ * estimator, tail-value and baseline calls, trpo_explained_variance, trpo_get_feed_view (whose old_dist
+ * then points at old_mean and n_actions is act_dim), the comm calls and profiling work unchanged.  The
+ * categorical-only calls (trpo_set_batch, trpo_action_dist, trpo_act, trpo_rollout_* and
+ * trpo_rollout_to_batch) on a Gaussian engine, and the three Gaussian calls on a categorical engine, return
+ * TRPO_ERR_STATE with a message that names the engine's distribution; nothing is launched. */
+#define TRPO_DIST_CATEGORICAL 0
+#define TRPO_DIST_GAUSSIAN 1
+/* trpo_create for either family; act_dim <= 128 (trpo_act_gaussian: <= 64) */
+int trpo_create_dist(trpo_engine** out, int dist, int obs_dim, const int* hidden, int n_hidden, int act_dim,
+                     int64_t max_rows, int device);
+int trpo_get_dist(trpo_engine* e, int* dist);
 void trpo_destroy(trpo_engine* e);
 const char* trpo_last_error(void);
 int64_t trpo_num_params(const trpo_engine* e);
@@ -125,6 +171,10 @@ int trpo_get_vector(trpo_engine* e, int which, float* out, int mem);
  * reduce_mean, trpo_inksci.py:48-51,56). */
 int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* states,
                    const int64_t* actions, const float* advant, const float* old_dist, int mem);
+/* the Gaussian engine's feed (TRPO_DIST_GAUSSIAN above): states [n][obs_dim], actions [n][act_dim], advant [n]
+ * (may be NULL, as above), old_mean [n][act_dim], old_logstd [act_dim], all f32 */
+int trpo_set_batch_gaussian(trpo_engine* e, int64_t n, int64_t n_global, const float* states, const float* actions,
+                            const float* advant, const float* old_mean, const float* old_logstd, int mem);
 /* rewards [n] f64, episode_starts [n] u8 (1 = first step of a path), baseline [n] f64 or NULL.
  * The paths of trpo_inksci.py:102-112, concatenated; this rank's shard must begin at a path start. */
 int trpo_set_rewards(trpo_engine* e, const double* rewards, const uint8_t* episode_starts,
@@ -175,6 +225,9 @@ int trpo_eval_losses(trpo_engine* e, const float* theta, float out3[3], int mem)
 /* session.run(self.action_dist) -> [n][n_actions] f32 at the current parameters
  * (trpo_inksci.py:38-40,78; the policy forward) */
 int trpo_action_dist(trpo_engine* e, float* out, int mem);
+/* the Gaussian policy forward at the current parameters over the feed: mean_out [n][act_dim] f32 and
+ * logstd_out [act_dim] f32 (either may be NULL) */
+int trpo_action_mean(trpo_engine* e, float* mean_out, float* logstd_out, int mem);
 /* session.run(self.pg) = flatgrad(surr, var_list) (trpo_inksci.py:54,146) */
 int trpo_policy_grad(trpo_engine* e, float* g_out, int mem);
 /* fisher_vector_product(p) = session.run(self.fvp) + cg_damping * p (trpo_inksci.py:56-70,124-126) */
@@ -386,7 +439,7 @@ typedef struct trpo_feed_view {
   int obs_dim, n_actions;
   const float* states;       /* [n][ld_states] f32 */
   int ld_states;
-  const float* old_dist;     /* [n][ld_old] f32 */
+  const float* old_dist;     /* [n][ld_old] f32; on a Gaussian engine the old mean */
   int ld_old;
   const uint8_t* episode_starts;   /* [n] */
   const double* returns;     /* [n] f64 after the advantages of this feed were computed, else NULL */
@@ -420,6 +473,12 @@ int trpo_explained_variance(trpo_engine* e, double* out);
  * trpo_act returns an error for it (and trpo_rollout_cartpole needs exactly 2 actions). */
 int trpo_act(trpo_engine* e, const float* states, int64_t n, const double* uniforms, int train, int64_t* actions_out,
              float* dists_out, int mem);
+/* the Gaussian policy's act on n states [n][obs_dim] f32: mean_out [n][act_dim] at the current parameters,
+ * logstd_out [act_dim], and actions_out [n][act_dim] = float32(mean + exp(logstd) * normals) with normals
+ * [n][act_dim] f64 (train = 1; the sum and product in float64) or the mean (train = 0, normals may be NULL).
+ * Any output may be NULL.  act_dim <= 64 here (one wave per state), as trpo_act. */
+int trpo_act_gaussian(trpo_engine* e, const float* states, int64_t n, const double* normals, int train,
+                      float* actions_out, float* mean_out, float* logstd_out, int mem);
 /* cat_sample(prob_nk) (utils.py:95-105) with the uniforms given: engine-free, current device */
 int trpo_cat_sample(const float* prob, int64_t n, int k, const double* uniforms, int64_t* out, int mem);
 /* one CartPole-v0 step per row (state [n][4] f64, action [n] i64); done = termination (not the TimeLimit) */

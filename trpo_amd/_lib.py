@@ -21,6 +21,8 @@ VEC_THETA, VEC_THETA_PREV, VEC_G, VEC_STEPDIR, VEC_FULLSTEP, VEC_THETA_LS = rang
 
 ADV_RETURNS, ADV_GAE = 0, 1
 
+DIST_CATEGORICAL, DIST_GAUSSIAN = 0, 1
+
 
 class UpdateParams(ctypes.Structure):
     _fields_ = [("cg_iters", c_int), ("residual_tol", c_float), ("cg_damping", c_float),
@@ -76,6 +78,8 @@ F32, F64 = 0, 1
 # name -> (restype, argtypes); every symbol include/trpo_engine.h declares
 SIGNATURES = {
     "trpo_create": (c_int, [POINTER(c_void_p), c_int, POINTER(c_int), c_int, c_int, c_int64, c_int]),
+    "trpo_create_dist": (c_int, [POINTER(c_void_p), c_int, c_int, POINTER(c_int), c_int, c_int, c_int64, c_int]),
+    "trpo_get_dist": (c_int, [c_void_p, POINTER(c_int)]),
     "trpo_destroy": (None, [c_void_p]),
     "trpo_last_error": (c_char_p, []),
     "trpo_num_params": (c_int64, [c_void_p]),
@@ -89,6 +93,8 @@ SIGNATURES = {
     "trpo_get_flat": (c_int, [c_void_p, c_void_p, c_int]),
     "trpo_get_vector": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "trpo_set_batch": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "trpo_set_batch_gaussian": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int]),
     "trpo_set_rewards": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "trpo_compute_advantages": (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_int]),
     "trpo_standardize": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int]),
@@ -99,6 +105,7 @@ SIGNATURES = {
     "trpo_losses": (c_int, [c_void_p, POINTER(c_float)]),
     "trpo_eval_losses": (c_int, [c_void_p, c_void_p, POINTER(c_float), c_int]),
     "trpo_action_dist": (c_int, [c_void_p, c_void_p, c_int]),
+    "trpo_action_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "trpo_policy_grad": (c_int, [c_void_p, c_void_p, c_int]),
     "trpo_fvp": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int]),
     "trpo_cg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, POINTER(c_int), c_int]),
@@ -136,6 +143,7 @@ SIGNATURES = {
     "trpo_explained_variance": (c_int, [c_void_p, POINTER(c_double)]),
     "trpo_rollout_to_batch": (c_int, [c_void_p, c_int64]),
     "trpo_act": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    "trpo_act_gaussian": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "trpo_cat_sample": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int]),
     "trpo_cartpole_step": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int]),
     # value-function baseline (utils.py:48-92)

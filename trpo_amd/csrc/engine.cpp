@@ -42,9 +42,19 @@ struct trpo_engine {
   int num_cus = 256;               // compute units of `device` (hipDeviceAttributeMultiprocessorCount)
   hipStream_t stream = nullptr;
   // policy shape
+  int dist = TRPO_DIST_CATEGORICAL;   // the policy's distribution family, fixed at creation
+  bool gauss() const { return dist == TRPO_DIST_GAUSSIAN; }
+  static const char* dist_name(int d) { return d == TRPO_DIST_GAUSSIAN ? "gaussian" : "categorical"; }
+  // a call that exists for one family only: a state error that names this engine's, before anything is launched
+  void require_dist(int want, const char* call) const {
+    if (dist != want)
+      throw std::runtime_error(std::string(call) + " needs a " + dist_name(want) + " engine; this engine's distribution is " +
+                               dist_name(dist));
+  }
   int L = 0;                       // layers
   std::vector<int> w, wp;          // widths [obs, hidden..., A] and padded
-  int64_t P = 0;
+  int64_t P = 0;                   // parameters: the layers' and, on a Gaussian engine, the A log-stds after them
+  const float* logstd_of(const float* th) const { return th + (P - w[L]); }
   std::vector<int64_t> offW, offb;
   int64_t cap = 0, n = 0, n_global = 0;
   // multi-GPU
@@ -68,7 +78,10 @@ struct trpo_engine {
   float* X = nullptr;
   float* stage = nullptr;   // staging for host inputs / compact outputs: cap rows of max(pad4(obs), pad4(A), 2) floats
   int* act = nullptr;
-  float *adv32 = nullptr, *old = nullptr;
+  float *adv32 = nullptr, *old = nullptr;   // old: the old distribution, or on a Gaussian engine the old mean
+  // Gaussian engine only: the actions [cap][pad4(A)], the old log-std [A] and the partials of g's log-std block
+  float *actf = nullptr, *logstd0 = nullptr;
+  double* gs_part = nullptr;
   double *rewards = nullptr, *returns = nullptr, *adv64 = nullptr, *baseline = nullptr;
   uint8_t* starts = nullptr;
   bool have_baseline = false, have_rewards = false;
@@ -176,7 +189,7 @@ struct trpo_engine {
     // a hidden layer below the head layer, wider than 128 (one thread per column: at 64 columns three
     // quarters of its lanes idle, and C3 ran 3 % slower than on the row GEMMs); E_{L-2} is written too
     // where the FVP path reads it (no fused tail)
-    return g_options.hbwd2 != 0 && L >= 3 && wp[L - 1] > 128 && head_bwd2_eligible(w[L], wp[L - 1]);
+    return !gauss() && g_options.hbwd2 != 0 && L >= 3 && wp[L - 1] > 128 && head_bwd2_eligible(w[L], wp[L - 1]);
   }
   int x_mpad = 0, x_ldp = 0;
   bool x_planes = false;   // Xh/Xl hold the current X
@@ -201,7 +214,7 @@ struct trpo_engine {
   uint16_t* tail_planes = nullptr;   // head planes of the fused FVP tail (tail.hip), [2][2][32][kTailK]
   // the fused last-layer tail: f16 split, last hidden width in (128, 256], 17..32 actions
   bool use_tail() const {
-    return g_options.tail != 0 && f16_split() && L >= 2 && tail_eligible(wp[L - 1], wp[L]) && w[L] <= 32;
+    return !gauss() && g_options.tail != 0 && f16_split() && L >= 2 && tail_eligible(wp[L - 1], wp[L]) && w[L] <= 32;
   }
   // whether the FVP path reads E_{L-2} (the plain tanh'' term under the last hidden layer): every path
   // but the fused tail, which recomputes it (tail.hip)
@@ -228,7 +241,7 @@ struct trpo_engine {
   // (~2 MB of bf16 planes per workgroup tile) costs more than the fusion saves
   // whole FVP (R-forward, head, R-backward and weight gradients) in one launch (fused.hip): one or
   // two hidden layers of width <= 64, obs <= 128, <= 32 actions; reuses the chain's weight images
-  bool use_fused() const { return g_options.fused != 0 && chain_otm > 0 && fused_fvp_eligible(L, w.data()); }
+  bool use_fused() const { return !gauss() && g_options.fused != 0 && chain_otm > 0 && fused_fvp_eligible(L, w.data()); }
   // the same launch on the f16 split (fused16.hip, option fused = 3): two hidden layers of width 49..64; its
   // own weight images (2 f16 planes, one scale exponent per job) and chunk table
   ImageSet f16_set;
@@ -236,7 +249,7 @@ struct trpo_engine {
   unsigned* cg_ticket = nullptr;  // cg_step_slabs_kernel's arrival ticket (zero between launches)
   // the line-search loss forward's images (W_0 | W_1 | W_2 of the trial vector, fwd_loss16)
   ImageSet f16_loss_set;
-  bool use_fused16() const { return g_options.fused == 3 && f16 && f16_set.img && fused16_eligible(L, w.data()); }
+  bool use_fused16() const { return !gauss() && g_options.fused == 3 && f16 && f16_set.img && fused16_eligible(L, w.data()); }
   // layer 1's R-backward (and the policy gradient's backward into layer 0) fused with layer 0's weight
   // gradient (rbwd0.hip): f16 split with X's planes, obs <= 128, first hidden width <= 256
   uint16_t* rf_img = nullptr;   // rfwd.hip's chunk image (V0^T, W1, V1 in the kernel's LDS order), per FVP
@@ -290,7 +303,7 @@ struct trpo_engine {
     return a;
   }
   bool use_chain() const {
-    return chain_otm > 0 && (g_options.chain >= 2 || (g_options.chain == 1 && chain_otm <= 8));
+    return !gauss() && chain_otm > 0 && (g_options.chain >= 2 || (g_options.chain == 1 && chain_otm <= 8));
   }
 
   // rollout (rollout.hip): per-environment regions, reallocated when a rollout needs more
@@ -402,10 +415,14 @@ struct trpo_engine {
   }
 
   // ------------------------------------------------------------------------
-  void init(int obs, const int* hidden, int nh, int A, int64_t max_rows, int dev) {
+  void init(int dist_id, int obs, const int* hidden, int nh, int A, int64_t max_rows, int dev) {
+    REQUIRE(dist_id == TRPO_DIST_CATEGORICAL || dist_id == TRPO_DIST_GAUSSIAN,
+            "dist must be TRPO_DIST_CATEGORICAL or TRPO_DIST_GAUSSIAN");
+    dist = dist_id;
     REQUIRE(obs > 0 && A > 0 && nh >= 0 && max_rows > 0, "invalid policy dimensions");
     REQUIRE(nh + 1 <= kMaxLayers, "too many layers");
-    REQUIRE(A <= 32 * kMaxHeadTiles, "n_actions must be <= 128 (softmax rows of up to 4 x 32 lanes)");
+    REQUIRE(A <= 32 * kMaxHeadTiles, gauss() ? "act_dim must be <= 128 (head rows of up to 4 x 32 lanes)"
+                                             : "n_actions must be <= 128 (softmax rows of up to 4 x 32 lanes)");
     REQUIRE(max_rows < (int64_t(1) << 31), "max_rows must fit in int32 row indices");
     for (int i = 0; i < nh; ++i) REQUIRE(hidden[i] > 0, "hidden widths must be positive");
     device = dev;
@@ -424,6 +441,7 @@ struct trpo_engine {
       offb.push_back(P);
       P += w[l + 1];
     }
+    if (gauss()) P += A;   // the log-std vector, last in the flat layout
     cap = max_rows;
 
     for (float** v : {&theta, &theta_prev, &theta_trial, &theta_ls, &g, &bneg, &x, &r, &p, &p2, &z, &hv,
@@ -534,10 +552,17 @@ struct trpo_engine {
       D1h = dalloc<uint16_t>((size_t)((cap + 255) / 256 * 256) * d1_ldp);
       eD1t = dalloc<int>((size_t)(cap + 31) / 32 + 8);
     }
+    if (gauss()) {
+      actf = dalloc<float>((size_t)cap * wp[L]);
+      logstd0 = dalloc<float>(wp[L]);
+      gs_part = dalloc<double>((size_t)kGaussColBlocks * 128);
+    }
     HIPCHECK(hipHostMalloc((void**)&hsc, sizeof(UpdScalars), hipHostMallocDefault));
     std::memset(hsc, 0, sizeof(UpdScalars));
-    setup_chain();
-    setup_fused16();
+    if (!gauss()) {   // the fused FVP kernels embed the softmax head
+      setup_chain();
+      setup_fused16();
+    }
     HIPCHECK(hipStreamSynchronize(stream));
   }
 
@@ -1020,6 +1045,7 @@ struct trpo_engine {
   // epilogue is `head`; hidden activations go to `hout`
   void forward(const WeightSet& ws, const float* th, const std::vector<float*>& hout, RowEpi head, const char* tag) {
     int l_first = 0;
+    const bool prep = head == RowEpi::kPrepHead || head == RowEpi::kGaussPrepHead;
     if (use_fwd01()) {   // layers 0 and 1 in one launch; H1 stored by the prepare pass only (the FVP reads it)
       {
         Scope sp(this, tag, "_img");
@@ -1035,7 +1061,7 @@ struct trpo_engine {
       fa.eX = pl_e;
       fa.b0 = th + offb[0];
       fa.b1 = th + offb[1];
-      fa.H1 = head == RowEpi::kPrepHead ? hout[1] : nullptr;
+      fa.H1 = prep ? hout[1] : nullptr;
       fa.H2 = hout[2];
       fa.img = fw_img;
       fa.am_w0 = am_w(ws, 0);
@@ -1055,7 +1081,7 @@ struct trpo_engine {
       // rows: C4 3.6 -> 3.1 ms); 2: the loss heads, and the prepare head for <= 8 actions
       const int hfo = g_options.head_fwd;
       const bool prep_hf = hfo == 1 || (hfo == 2 && w[L] <= 8);
-      if (l == L - 1 && (hfo == 1 || hfo == 2) && head_fwd_eligible(w[L], w[L - 1]) &&
+      if (l == L - 1 && !gauss() && (hfo == 1 || hfo == 2) && head_fwd_eligible(w[L], w[L - 1]) &&
           ((head == RowEpi::kPrepHead && prep_hf) || head == RowEpi::kLossHead)) {
         // the softmax head with one state per lane (hbwd.hip): bound by its read of H_{L-1}
         HeadFwdArgs hf{};
@@ -1104,6 +1130,12 @@ struct trpo_engine {
           a.ea.amax1 = am_d(L - 1);
           a.ea.amax2 = am_ds(L - 1);
         }
+        if (gauss()) {   // out1 (D_{L-1}'s buffer, free here) takes the rows of g's log-std block
+          a.ea.actf = actf;
+          a.ea.logstd = logstd_of(th);
+          a.ea.logstd0 = logstd0;
+          if (prep) a.ea.amax2 = am_ds(L - 1);
+        }
       }
       Scope sp(this, tag, l);
       launch_rowgemm(a, stream);
@@ -1121,6 +1153,41 @@ struct trpo_engine {
   }
 
   void require_batch() { REQUIRE(n > 0, "no batch: call trpo_set_batch first"); }
+
+  // a caller's [n][width] f32 rows of the feed -> dst [n][ldp] (padding columns stay zero)
+  void stage_rows(const float* src, int width, int ldp, float* dst, int mem) {
+    if (width == ldp) {
+      copy_in(dst, src, (size_t)n * width * sizeof(float), mem);
+      return;
+    }
+    // (a stream-ordered hipMallocAsync temporary here lost the pageable host copy on its first
+    // use in the VF runtime; persistent staging avoids the pattern)
+    const float* s = src;
+    if (mem != TRPO_MEM_DEVICE) {
+      copy_in(stage, src, (size_t)n * width * sizeof(float), mem);
+      s = stage;
+    }
+    launch_copy_rows(s, n, width, width, dst, ldp, stream);
+    check_launch();
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  // the prepare head's first output (the softmax, or the Gaussian mean) of the feed's rows -> out [n][A]
+  void fetch_head_rows(float* out, int mem) {
+    const int A = w[L];
+    float* dst = mem == TRPO_MEM_DEVICE ? out : stage;
+    launch_copy_rows(Pm, n, A, wp[L], dst, A, stream);
+    check_launch();
+    if (mem != TRPO_MEM_DEVICE) copy_out(out, stage, (size_t)n * A * sizeof(float), mem);
+    HIPCHECK(hipStreamSynchronize(stream));
+  }
+  // a new feed is in place: the split geometry follows its rows, nothing derived from the old feed survives
+  void feed_loaded() {
+    set_splits();
+    cache.batch_changed();
+    have_rewards = false;
+    have_tail = false;
+    feed_is_rollout = false;
+  }
 
   void update_x_amax() {
     if (!f16) return;
@@ -1146,6 +1213,15 @@ struct trpo_engine {
     // path changes)
     cache.prepare_begins(e_top_needed(), use_fused16());
     ensure_w3();
+    if (gauss()) {
+      // the forward and the prepare head only: at theta = theta_old KL_ff's plain backward is exactly zero
+      // (D_l = 0, E_l = 0), so nothing below the head is written and the FVP drops those terms
+      am_reset(am_ds(L - 1), 1);
+      forward(cur_set(), theta, H, RowEpi::kGaussPrepHead, "fwd");
+      reduce_losses(0, nullptr);
+      cache.prepared = true;
+      return;
+    }
     am_reset(am_d(0), L);
     am_reset(am_ds(L - 1), 1);
     if (use_fused16() && g_options.ls_fused == 1) fused16_forward(theta, true);   // fwd_loss16's prepare form
@@ -1236,10 +1312,24 @@ struct trpo_engine {
   }
 
   // sum over splits -> out (local partial) ; all-reduce
-  void reduce_grad(float* out, const int* skip, int slabs = 0) {
+  // Gaussian engine: the log-std block of `out` (no launch writes it into the slabs) as this rank's partial, from the
+  // tangent's block (Hv_s = 2 v_s n / N) or, v_tail = NULL, from the prepare head's rows (g_s)
+  void reduce_grad(float* out, const int* skip, int slabs = 0, const float* v_tail = nullptr) {
     {
       Scope sp(this, "reduce");
       launch_reduce_slab(slab, slabs > 0 ? slabs : active_splits, slab_stride, P, out, skip, stream);
+      check_launch();
+    }
+    if (gauss()) {
+      Scope sp(this, "logstd_block");
+      const int A = w[L];
+      float* tail = out + (P - A);
+      if (v_tail) {
+        launch_gauss_scale_tail(v_tail, A, 2.0 * (double)n / (double)n_global, tail, skip, stream);
+      } else {
+        const int blocks = launch_gauss_colsum_partials(D[L - 1], n, A, wp[L], gs_part, stream);
+        launch_gauss_colsum_finish(gs_part, blocks, A, -1.0 / (double)n_global, tail, skip, stream);
+      }
       check_launch();
     }
     allreduce_f32(out, (size_t)P);
@@ -1356,7 +1446,10 @@ struct trpo_engine {
       check_launch();
     }
     ensure_w3();
-    split_parts(false, true, false, true, cur_set(), skip, "split_v");
+    // Gaussian engine: D_l = E_l = 0, so the R-backward is the policy gradient's (RD_l W_l^T alone: no V^T planes)
+    // and each weight gradient one segment, H_l^T RD_l
+    const bool gs = gauss();
+    split_parts(false, true, false, !gs, cur_set(), skip, "split_v");
     am_reset(am_rh(0), L);
     am_reset(am_rd(0), L);
     // R-forward (the fused tail takes the last layer's)
@@ -1420,8 +1513,9 @@ struct trpo_engine {
         a.ea.out0 = RH[l + 1];
         a.ea.amax0 = am_rh(l + 1);
       } else {
-        a.epi = RowEpi::kRHead;
+        a.epi = gs ? RowEpi::kGaussRHead : RowEpi::kRHead;
         a.ea.P = Pm;
+        a.ea.logstd = gs ? logstd_of(theta) : nullptr;
         a.ea.out0 = RD[L - 1];
         a.ea.amax0 = am_rd(L - 1);
         a.ea.invN = 1.0 / (double)n_global;
@@ -1475,6 +1569,31 @@ struct trpo_engine {
     const bool r0f = use_rbwd0() && Lf - 1 >= 1;
     // R-backward: RDH_l = RD_l W_l^T + D_l V_l^T ; RD_{l-1} = RDH (1-H_l^2) + E_{l-1} RH_l
     for (int l = Lf - 1; l >= 1; --l) {
+      if (l == 1 && r0f && gs) {
+        RBwd0Args a = rbwd0_args(skip);   // the nseg = 1 form: RD_0 = (RD_1 W_1^T)(1 - H_1^2), X^T RD_0 to the slab
+        a.nseg = 1;
+        a.A0 = RD[1];
+        a.am_a0 = am_rd(1);
+        Scope sp(this, "fvp_rbwdwg_l1");
+        launch_rbwd0(a, stream);
+        check_launch();
+        continue;
+      }
+      if (gs) {
+        RowGemmArgs a = row_args(w[l], wp[l]);
+        a.nseg = 1;
+        a.seg[0] = bwd_seg(l, kW, RD[l], am_rd(l));
+        a.skip = skip;
+        a.epi = RowEpi::kPgBwd;
+        a.ea.H = H[l];
+        a.ea.out0 = RD[l - 1];
+        a.ea.amax0 = am_rd(l - 1);
+        a.ea.ldo = wp[l];
+        Scope sp(this, "fvp_rbwd", l);
+        launch_rowgemm(a, stream);
+        check_launch();
+        continue;
+      }
       if (l == 1 && r0f) {
         RBwd0Args a = rbwd0_args(skip);
         a.nseg = 2;
@@ -1511,6 +1630,13 @@ struct trpo_engine {
       Scope sp(this, "fvp_rbwd", l);
       launch_rowgemm(a, stream);
       check_launch();
+    }
+    if (gs) {
+      for (int l = r0f ? 1 : 0; l < L; ++l)
+        wgrad_layer(l, 1, WSeg{act_in(l), RD[l], wp[l], wp[l + 1], l == 0 ? am_x() : nullptr, am_rd(l)}, WSeg{}, 0, skip,
+                    "fvp_wgrad");
+      reduce_grad(out, skip, 0, v + (P - w[L]));
+      return;
     }
     fvp_wgrads(r0f ? 1 : 0, Lf, skip, rh1p);
     reduce_grad(out, skip);
@@ -1768,7 +1894,7 @@ struct trpo_engine {
     PackArgs pa = pack_args(WFt, nullptr, 2);
     launch_pack(pa, th, 0, nullptr, stream);
     split_parts(true, false, false, false, trial_set(), nullptr, "split_t");
-    forward(trial_set(), th, RH, RowEpi::kLossHead, "ls_fwd");
+    forward(trial_set(), th, RH, gauss() ? RowEpi::kGaussLossHead : RowEpi::kLossHead, "ls_fwd");
     reduce_losses(1, nullptr);
   }
 
@@ -2022,19 +2148,31 @@ extern "C" {
 
 const char* trpo_last_error(void) { return g_last_error.c_str(); }
 
-int trpo_create(trpo_engine** out, int obs_dim, const int* hidden, int n_hidden, int n_actions,
-                int64_t max_rows, int device) {
+int trpo_create_dist(trpo_engine** out, int dist, int obs_dim, const int* hidden, int n_hidden, int act_dim,
+                     int64_t max_rows, int device) {
   return guarded([&] {
     REQUIRE(out, "out is NULL");
     REQUIRE(n_hidden == 0 || hidden, "hidden is NULL");
     auto e = std::make_unique<trpo_engine>();
     try {
-      e->init(obs_dim, hidden, n_hidden, n_actions, max_rows, device);
+      e->init(dist, obs_dim, hidden, n_hidden, act_dim, max_rows, device);
     } catch (...) {
       e->release();
       throw;
     }
     *out = e.release();
+  });
+}
+
+int trpo_create(trpo_engine** out, int obs_dim, const int* hidden, int n_hidden, int n_actions,
+                int64_t max_rows, int device) {
+  return trpo_create_dist(out, TRPO_DIST_CATEGORICAL, obs_dim, hidden, n_hidden, n_actions, max_rows, device);
+}
+
+int trpo_get_dist(trpo_engine* e, int* dist) {
+  return guarded([&] {
+    REQUIRE(e && dist, "NULL argument");
+    *dist = e->dist;
   });
 }
 
@@ -2165,6 +2303,7 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
                    const int64_t* actions, const float* advant, const float* old_dist, int mem) {
   return guarded([&] {
     REQUIRE(e && states && actions && old_dist, "NULL argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_set_batch");
     REQUIRE(n > 0 && n <= e->cap, "n out of range (0 < n <= max_rows)");
     REQUIRE(n_global >= n, "n_global must be >= n");
     e->use();
@@ -2172,24 +2311,8 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
     e->n_global = n_global;
     const int obs = e->w[0], A = e->w[e->L];
     // states -> [n][pad4(obs)], old_dist -> [n][pad4(A)] (padding zero)
-    auto stage = [&](const float* src, int width, int ldp, float* dst) {
-      if (width == ldp) {
-        e->copy_in(dst, src, (size_t)n * width * sizeof(float), mem);
-        return;
-      }
-      // (a stream-ordered hipMallocAsync temporary here lost the pageable host copy on its first
-      // use in the VF runtime; persistent staging avoids the pattern)
-      const float* s = src;
-      if (mem != TRPO_MEM_DEVICE) {
-        e->copy_in(e->stage, src, (size_t)n * width * sizeof(float), mem);
-        s = e->stage;
-      }
-      launch_copy_rows(s, n, width, width, dst, ldp, e->stream);
-      check_launch();
-      HIPCHECK(hipStreamSynchronize(e->stream));
-    };
-    stage(states, obs, e->wp[0], e->X);
-    stage(old_dist, A, e->wp[e->L], e->old);
+    e->stage_rows(states, obs, e->wp[0], e->X, mem);
+    e->stage_rows(old_dist, A, e->wp[e->L], e->old, mem);
     e->update_x_amax();
     const int64_t* acts = actions;
     if (mem != TRPO_MEM_DEVICE) {
@@ -2203,11 +2326,28 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
     e->copy_out(&bad, e->dbad, sizeof(int), TRPO_MEM_HOST);
     REQUIRE(!bad, "action index out of range [0, n_actions)");
     if (advant) e->copy_in(e->adv32, advant, (size_t)n * sizeof(float), mem);
-    e->set_splits();
-    e->cache.batch_changed();
-    e->have_rewards = false;
-    e->have_tail = false;
-    e->feed_is_rollout = false;
+    e->feed_loaded();
+  });
+}
+
+int trpo_set_batch_gaussian(trpo_engine* e, int64_t n, int64_t n_global, const float* states, const float* actions,
+                            const float* advant, const float* old_mean, const float* old_logstd, int mem) {
+  return guarded([&] {
+    REQUIRE(e && states && actions && old_mean && old_logstd, "NULL argument");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_set_batch_gaussian");
+    REQUIRE(n > 0 && n <= e->cap, "n out of range (0 < n <= max_rows)");
+    REQUIRE(n_global >= n, "n_global must be >= n");
+    e->use();
+    e->n = n;
+    e->n_global = n_global;
+    const int A = e->w[e->L], ldA = e->wp[e->L];
+    e->stage_rows(states, e->w[0], e->wp[0], e->X, mem);
+    e->stage_rows(actions, A, ldA, e->actf, mem);
+    e->stage_rows(old_mean, A, ldA, e->old, mem);
+    e->copy_in(e->logstd0, old_logstd, (size_t)A * sizeof(float), mem);
+    e->update_x_amax();
+    if (advant) e->copy_in(e->adv32, advant, (size_t)n * sizeof(float), mem);
+    e->feed_loaded();
   });
 }
 
@@ -2346,14 +2486,21 @@ int trpo_eval_losses(trpo_engine* e, const float* theta, float out3[3], int mem)
 int trpo_action_dist(trpo_engine* e, float* out, int mem) {
   return guarded([&] {
     REQUIRE(e && out, "NULL argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_action_dist");
     e->use();
     e->prepare();
-    const int A = e->w[e->L];
-    float* dst = mem == TRPO_MEM_DEVICE ? out : e->stage;
-    launch_copy_rows(e->Pm, e->n, A, e->wp[e->L], dst, A, e->stream);
-    check_launch();
-    if (mem != TRPO_MEM_DEVICE) e->copy_out(out, e->stage, (size_t)e->n * A * sizeof(float), mem);
-    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->fetch_head_rows(out, mem);
+  });
+}
+
+int trpo_action_mean(trpo_engine* e, float* mean_out, float* logstd_out, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_action_mean");
+    e->use();
+    e->prepare();
+    if (mean_out) e->fetch_head_rows(mean_out, mem);
+    if (logstd_out) e->copy_out(logstd_out, e->logstd_of(e->theta), (size_t)e->w[e->L] * sizeof(float), mem);
   });
 }
 
@@ -2519,6 +2666,7 @@ int trpo_rollout_env(trpo_engine* e, int env, const trpo_rollout_params* p, int6
                      int64_t* n_paths_out) {
   return guarded([&] {
     REQUIRE(e && p, "NULL argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_env");
     e->use();
     e->rollout(env, *p);
     if (n_steps_out) *n_steps_out = e->roll_n;
@@ -2533,6 +2681,7 @@ int trpo_rollout_cartpole(trpo_engine* e, const trpo_rollout_params* p, int64_t*
 int trpo_rollout_fetch_states(trpo_engine* e, double* env_states, int mem) {
   return guarded([&] {
     REQUIRE(e, "NULL argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_fetch_states");
     if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
     REQUIRE(env_states, "NULL argument");
     e->use();
@@ -2549,6 +2698,7 @@ int trpo_rollout_fetch(trpo_engine* e, double* obs, float* obs32, int64_t* actio
                        double* rewards, uint8_t* episode_starts, double* uniforms, int mem) {
   return guarded([&] {
     REQUIRE(e, "NULL argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_fetch");
     REQUIRE(e->roll_valid, "no rollout to fetch");
     e->use();
     const int64_t N = e->roll_n;
@@ -2572,6 +2722,7 @@ int trpo_rollout_fetch(trpo_engine* e, double* obs, float* obs32, int64_t* actio
 int trpo_rollout_to_batch(trpo_engine* e, int64_t n_global) {
   return guarded([&] {
     REQUIRE(e, "NULL argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_to_batch");
     REQUIRE(e->roll_valid, "no rollout to load");
     const int64_t N = e->roll_n;
     REQUIRE(N <= e->cap, "rollout has more steps than max_rows");
@@ -2630,6 +2781,7 @@ int trpo_rollout_fetch_ends(trpo_engine* e, uint8_t* truncated, double* final_ob
                             int64_t* lengths, int64_t* end_rows, int mem) {
   return guarded([&] {
     REQUIRE(e, "NULL argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_fetch_ends");
     if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
     e->use();
     const int64_t P = e->roll_paths;
@@ -2694,6 +2846,7 @@ int trpo_act(trpo_engine* e, const float* states, int64_t n, const double* unifo
              float* dists_out, int mem) {
   return guarded([&] {
     REQUIRE(e && states && n >= 0, "bad argument");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_act");
     REQUIRE(!train || uniforms, "train = 1 needs uniforms (cat_sample's np.random.rand)");
     REQUIRE(e->w[e->L] <= 64, "act: n_actions must be <= 64 (one wave per state)");
     e->use();
@@ -2705,6 +2858,30 @@ int trpo_act(trpo_engine* e, const float* states, int64_t n, const double* unifo
     int64_t* ao = st.out(actions_out, (size_t)n);
     float* dout = st.out(dists_out, (size_t)n * A);
     launch_act(e->policy_shape(), e->theta, e->max_width(), s, n, r, train, ao, dout, e->stream);
+    check_launch();
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int trpo_act_gaussian(trpo_engine* e, const float* states, int64_t n, const double* normals, int train,
+                      float* actions_out, float* mean_out, float* logstd_out, int mem) {
+  return guarded([&] {
+    REQUIRE(e && states && n >= 0, "bad argument");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_act_gaussian");
+    REQUIRE(!train || normals, "train = 1 needs normals [n][act_dim]");
+    REQUIRE(e->w[e->L] <= 64, "act_gaussian: act_dim must be <= 64 (one wave per state)");
+    e->use();
+    const int obs = e->w[0], A = e->w[e->L];
+    if (logstd_out) e->copy_out(logstd_out, e->logstd_of(e->theta), (size_t)A * sizeof(float), mem);
+    if (n == 0) return;
+    Staging st(mem, e->stream);
+    const float* s = st.in(states, (size_t)n * obs);
+    const double* xi = st.in(normals, (size_t)n * A);
+    float* ao = st.out(actions_out, (size_t)n * A);
+    float* mo = st.out(mean_out, (size_t)n * A);
+    launch_act_gaussian(e->policy_shape(), e->theta, e->logstd_of(e->theta), e->max_width(), s, n, xi, train, ao, mo,
+                        e->stream);
     check_launch();
     st.fetch();
     HIPCHECK(hipStreamSynchronize(e->stream));

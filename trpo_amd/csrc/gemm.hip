@@ -1035,7 +1035,7 @@ template <int EPI>
 void launch_row_epi(const RowGemmArgs& a, hipStream_t s) {
   if constexpr (epi_is_head(EPI)) {
     // one 32-column tile per 32 actions in every lane half (epi_row)
-    if (a.N > 32 * kMaxHeadTiles) throw std::runtime_error("softmax head supports at most 128 actions");
+    if (a.N > 32 * kMaxHeadTiles) throw std::runtime_error("a row-wise head supports at most 128 actions");
     if (a.N > 64) launch_row_cfg<4, 1, 2, 4, 16, EPI>(a, s);
     else if (a.N > 32) launch_row_cfg<4, 1, 2, 2, 16, EPI>(a, s);
     else launch_row_cfg<4, 1, 2, 1, 16, EPI>(a, s);
@@ -1128,6 +1128,9 @@ void launch_rowgemm(const RowGemmArgs& a, hipStream_t s) {
     case RowEpi::kPrepHead: launch_row_epi<(int)RowEpi::kPrepHead>(a, s); break;
     case RowEpi::kLossHead: launch_row_epi<(int)RowEpi::kLossHead>(a, s); break;
     case RowEpi::kRHead: launch_row_epi<(int)RowEpi::kRHead>(a, s); break;
+    case RowEpi::kGaussPrepHead: launch_row_epi<(int)RowEpi::kGaussPrepHead>(a, s); break;
+    case RowEpi::kGaussLossHead: launch_row_epi<(int)RowEpi::kGaussLossHead>(a, s); break;
+    case RowEpi::kGaussRHead: launch_row_epi<(int)RowEpi::kGaussRHead>(a, s); break;
     case RowEpi::kRelu: launch_row_epi<(int)RowEpi::kRelu>(a, s); break;
     case RowEpi::kReluBwd: launch_row_epi<(int)RowEpi::kReluBwd>(a, s); break;
   }

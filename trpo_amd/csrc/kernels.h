@@ -115,10 +115,17 @@ enum class RowEpi : int {
   kRZ = 11,       // RZ = acc + bias                             (R-forward pre-activation of the last
                   //                                              hidden layer: the fused tail applies
                   //                                              (1-H^2) as it loads H, so H is read once)
+  // the diagonal-Gaussian heads (include/trpo_engine.h, TRPO_DIST_GAUSSIAN), in the softmax heads' lane layout
+  kGaussPrepHead = 12,  // mean, DS_L, adv r (z^2 - 1) rows, row loss terms  (prepare)
+  kGaussLossHead = 13,  // row loss terms only                               (line search)
+  kGaussRHead = 14,     // RD_L = (acc + c) / (sigma^2 N)                    (FVP)
 };
-// the row-wise softmax heads (one output row per 32-lane wave half, up to kMaxHeadTiles 32-column tiles)
+// the row-wise heads (one output row per 32-lane wave half, up to kMaxHeadTiles 32-column tiles)
 constexpr int kMaxHeadTiles = 4;
-constexpr bool epi_is_head(int e) { return e >= (int)RowEpi::kPrepHead && e <= (int)RowEpi::kRHead; }
+constexpr bool epi_is_gauss(int e) { return e >= (int)RowEpi::kGaussPrepHead && e <= (int)RowEpi::kGaussRHead; }
+constexpr bool epi_is_head(int e) {
+  return (e >= (int)RowEpi::kPrepHead && e <= (int)RowEpi::kRHead) || epi_is_gauss(e);
+}
 
 struct RowEpiArgs {
   const float* bias;   // [N] (kTanh, kRHidden, heads)
@@ -141,6 +148,10 @@ struct RowEpiArgs {
   unsigned* amax0 = nullptr;
   unsigned* amax1 = nullptr;
   unsigned* amax2 = nullptr;
+  // Gaussian heads: `old` is the old mean, out0 the mean, out1 the rows adv r (z^2 - 1), out2 DS_L
+  const float* actf = nullptr;     // [M][ldo] actions (kGaussPrepHead, kGaussLossHead)
+  const float* logstd = nullptr;   // [N] log-std at the evaluated parameters
+  const float* logstd0 = nullptr;  // [N] old log-std (kGaussPrepHead, kGaussLossHead)
 };
 
 struct RowGemmArgs {
@@ -832,10 +843,33 @@ void launch_rollout_compact(const RolloutArgs& a, const int64_t* offsets, const 
                             hipStream_t s);
 void launch_act(const PolicyShape& ps, const float* theta, int maxw, const float* states, int64_t n, const double* r,
                 int train, int64_t* actions, float* dists, hipStream_t s);
+// The Gaussian policy's act on n states (one wave per state, act_dim <= 64): mean = the same wave forward without
+// the softmax, actions = float32(mean + exp(logstd) * normals) in float64 (train) or the mean; `normals` [n][A] f64
+// may be NULL when train = 0, either output may be NULL
+void launch_act_gaussian(const PolicyShape& ps, const float* theta, const float* logstd, int maxw, const float* states,
+                         int64_t n, const double* normals, int train, float* actions, float* means, hipStream_t s);
 void launch_cat_sample(const float* prob, int64_t n, int k, const double* r, int64_t* out, hipStream_t s);
 void launch_cartpole_step(const double* state, const int64_t* action, int64_t n, double* state_out, double* reward,
                           uint8_t* done, hipStream_t s);
 // state [n][state_dim] -> state_out, obs_out [n][obs_dim], reward, done (termination); outputs may be NULL
 void launch_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out,
                      double* obs_out, double* reward, uint8_t* done, hipStream_t s);
+}  // namespace trpo
+
+namespace trpo {
+// ---------------------------------------------------------------------------
+// The log-std blocks of a Gaussian engine's P-long vectors (gauss.hip).  The per-layer launches write the
+// network blocks into the slabs; these write the last A entries of the reduced vector, this rank's partial,
+// before the all-reduce.  Fixed-order f64 sums, no float atomics, no host synchronisation.
+// ---------------------------------------------------------------------------
+constexpr int kGaussColBlocks = 256;   // partial rows of the column reduction (fixed: the sum order depends on n only)
+// part[b][c] = sum over block b's rows of src[r][c], c < A <= 128; part holds kGaussColBlocks x 128 doubles.
+// Returns the blocks used (<= kGaussColBlocks), a function of n alone.
+int launch_gauss_colsum_partials(const float* src, int64_t n, int A, int ld, double* part, hipStream_t s);
+// out_tail[c] = f32(scale * sum_b part[b][c]), b < blocks in order
+void launch_gauss_colsum_finish(const double* part, int blocks, int A, double scale, float* out_tail, const int* skip,
+                                hipStream_t s);
+// out_tail[c] = f32(scale * v_tail[c])   (Hv's log-std block: scale = 2 n / N)
+void launch_gauss_scale_tail(const float* v_tail, int A, double scale, float* out_tail, const int* skip,
+                             hipStream_t s);
 }  // namespace trpo

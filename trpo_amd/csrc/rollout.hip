@@ -243,9 +243,10 @@ __device__ __forceinline__ float wave_sumf(float v) {
   return v;
 }
 
-// h_{l} = tanh(h_{l-1} W_l + b_l) ... p = softmax(z_L) (trpo_inksci.py:38-40); `in` holds the
-// obs (w[0] floats) on entry; returns this lane's p (lanes >= A: 0).  All lanes must call.
-__device__ float wave_policy(const PolicyShape& ps, const float* theta, float* in, float* out, int lane) {
+// h_{l} = tanh(h_{l-1} W_l + b_l), the last layer linear (trpo_inksci.py:38-39); `in` holds the obs (w[0]
+// floats) on entry; returns the slice that holds the last layer's outputs z_L.  All lanes must call.
+__device__ __forceinline__ float* wave_layers(const PolicyShape& ps, const float* theta, float* in, float* out,
+                                              int lane) {
   for (int l = 0; l < ps.L; ++l) {
     const int a = ps.w[l], b = ps.w[l + 1];
     const float* W = theta + ps.offW[l];
@@ -262,6 +263,12 @@ __device__ float wave_policy(const PolicyShape& ps, const float* theta, float* i
     in = out;
     out = t;
   }
+  return in;
+}
+
+// ... p = softmax(z_L) (trpo_inksci.py:40); returns this lane's p (lanes >= A: 0).  All lanes must call.
+__device__ float wave_policy(const PolicyShape& ps, const float* theta, float* in, float* out, int lane) {
+  in = wave_layers(ps, theta, in, out, lane);
   // softmax over A <= 64 logits, now in `in`
   const int A = ps.w[ps.L];
   const float z = lane < A ? in[lane] : -INFINITY;
@@ -450,6 +457,37 @@ __global__ void __launch_bounds__(kRollWaves * 64) act_kernel(const PolicyShape 
   if (lane == 0 && actions) actions[row] = action;
 }
 
+// the diagonal-Gaussian policy's act (one wave per state): the same wave forward without the softmax, then
+// a = float32(mu + exp(s) * xi) in float64 (train) or a = mu (include/trpo_engine.h, TRPO_DIST_GAUSSIAN)
+__global__ void __launch_bounds__(kRollWaves * 64) act_gaussian_kernel(const PolicyShape ps, const float* theta,
+                                                                       const float* logstd, int maxw,
+                                                                       const float* states, int64_t n,
+                                                                       const double* normals, int train,
+                                                                       float* actions, float* means) {
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * kRollWaves + wv;
+  if (row >= n) return;
+  float* buf0 = lds + (size_t)wv * 2 * maxw;
+  float* buf1 = buf0 + maxw;
+  const int obs_dim = ps.w[0], A = ps.w[ps.L];
+  for (int c = lane; c < obs_dim; c += 64) buf0[c] = states[row * obs_dim + c];
+  wave_sync();
+  const float* mu = wave_layers(ps, theta, buf0, buf1, lane);
+  if (lane < A) {
+    const float m = mu[lane];
+    if (means) means[row * A + lane] = m;
+    if (actions) {
+      float a = m;
+      if (train) {
+        const double noise = exp((double)logstd[lane]) * normals[row * A + lane];
+        a = (float)((double)m + noise);
+      }
+      actions[row * A + lane] = a;
+    }
+  }
+}
+
 __global__ void __launch_bounds__(256) cat_sample_kernel(const float* prob, int64_t n, int k, const double* r,
                                                          int64_t* out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -539,6 +577,15 @@ void launch_act(const PolicyShape& ps, const float* theta, int maxw, const float
   if (n <= 0) return;
   hipLaunchKernelGGL(act_kernel, dim3((unsigned)((n + kRollWaves - 1) / kRollWaves)), dim3(kRollWaves * 64),
                      rollout_lds_bytes(maxw), s, ps, theta, maxw, states, n, r, train, actions, dists);
+}
+
+void launch_act_gaussian(const PolicyShape& ps, const float* theta, const float* logstd, int maxw, const float* states,
+                         int64_t n, const double* normals, int train, float* actions, float* means, hipStream_t s) {
+  if (n <= 0) return;
+  if (ps.w[ps.L] > 64) throw std::invalid_argument("launch_act_gaussian: act_dim must be <= 64 (one wave per state)");
+  if (train && !normals) throw std::invalid_argument("launch_act_gaussian: train = 1 needs normals");
+  hipLaunchKernelGGL(act_gaussian_kernel, dim3((unsigned)((n + kRollWaves - 1) / kRollWaves)), dim3(kRollWaves * 64),
+                     rollout_lds_bytes(maxw), s, ps, theta, logstd, maxw, states, n, normals, train, actions, means);
 }
 
 void launch_cat_sample(const float* prob, int64_t n, int k, const double* r, int64_t* out, hipStream_t s) {

@@ -258,6 +258,113 @@ __device__ __forceinline__ void epi_row(const RowEpiArgs& e, int row, bool rowva
   }
 }
 
+// ---------------------------------------------------------------------------
+// row-wise diagonal-Gaussian head epilogues (include/trpo_engine.h, TRPO_DIST_GAUSSIAN), in the softmax heads'
+// lane layout.  The mean is the f32 accumulator plus bias; everything formed from it (z, z0, the log-ratio, the KL
+// and entropy terms) is f64: the KL and the log-ratio are differences of near-equal terms.  What depends on the
+// column alone is computed once per thread (gauss_cols), not per row.
+// ---------------------------------------------------------------------------
+template <int TN>
+struct GaussCols {
+  float bias[TN];
+  double s[TN], s0[TN];      // log-std, old log-std
+  double is[TN], is0[TN];    // 1 / sigma, 1 / sigma0
+  double k[TN];              // prep / loss: sigma0^2 / sigma^2 ; R head: 1 / (sigma^2 N)
+};
+template <int EPI, int TN>
+__device__ __forceinline__ GaussCols<TN> gauss_cols(const RowEpiArgs& e, int lr, int A) {
+  GaussCols<TN> c;
+#pragma unroll
+  for (int t = 0; t < TN; ++t) {
+    const int col = 32 * t + lr;
+    const int cc = col < A ? col : 0;
+    c.bias[t] = e.bias[cc];
+    c.s[t] = (double)e.logstd[cc];
+    c.is[t] = exp(-c.s[t]);
+    if constexpr (EPI == (int)RowEpi::kGaussRHead) {
+      c.s0[t] = c.s[t];
+      c.is0[t] = c.is[t];
+      c.k[t] = c.is[t] * c.is[t] * e.invN;
+    } else {
+      c.s0[t] = (double)e.logstd0[cc];
+      c.is0[t] = exp(-c.s0[t]);
+      c.k[t] = exp(2.0 * (c.s0[t] - c.s[t]));
+    }
+  }
+  return c;
+}
+
+template <int EPI, int TN>
+__device__ __forceinline__ void epi_row_gauss(const RowEpiArgs& e, const GaussCols<TN>& c, int row, bool rowvalid,
+                                              int lr, int A, const float (&v)[TN], float& m0, float& m2) {
+  // `row` is clamped into [0, M) by the caller, columns into [0, ldo): loads are unconditional, masked by selects
+  bool real[TN], st[TN];
+  size_t idx[TN];
+#pragma unroll
+  for (int t = 0; t < TN; ++t) {
+    const int col = 32 * t + lr;
+    real[t] = col < A;
+    const int colc = col < e.ldo ? col : e.ldo - 1;
+    idx[t] = (size_t)row * e.ldo + colc;
+    st[t] = rowvalid && col < e.ldo;
+  }
+  if constexpr (EPI == (int)RowEpi::kGaussRHead) {
+    // RD_L = R{mu} / (sigma^2 N), R{mu} = acc + c (the tangent bias)
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      const float rd = real[t] ? (float)((double)(v[t] + c.bias[t]) * c.k[t]) : 0.0f;
+      if (st[t]) {
+        e.out0[(size_t)row * e.ldo + 32 * t + lr] = rd;
+        m0 = fmaxf(m0, fabsf(rd));
+      }
+    }
+  } else {
+    const float advv = e.adv[row];
+    float mu[TN];
+    double z[TN], lrp = 0.0, klp = 0.0, enp = 0.0;
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      const float av = e.actf[idx[t]], m0v = e.old[idx[t]];
+      mu[t] = v[t] + c.bias[t];
+      const bool on = rowvalid && real[t];
+      const double a = (double)av, mud = (double)mu[t], mu0 = (double)m0v;
+      z[t] = on ? (a - mud) * c.is[t] : 0.0;
+      const double z0 = on ? (a - mu0) * c.is0[t] : 0.0;
+      const double dm = on ? (mu0 - mud) * c.is[t] : 0.0;
+      // log r = sum_d (s0 - s) + (z0^2 - z^2)/2 ; KL(old || new) ; entropy
+      lrp += on ? (c.s0[t] - c.s[t]) + 0.5 * (z0 * z0 - z[t] * z[t]) : 0.0;
+      klp += on ? (c.s[t] - c.s0[t]) + 0.5 * (c.k[t] + dm * dm) - 0.5 : 0.0;
+      enp += on ? c.s[t] + 1.4189385332046727 : 0.0;   // 0.5 ln(2 pi e)
+    }
+    const double logr = sum32<TRPO_HEAD_DPP>(lrp);
+    const double klt = sum32<TRPO_HEAD_DPP>(klp);
+    const double ent = sum32<TRPO_HEAD_DPP>(enp);
+    const double ar = rowvalid ? (double)advv * exp(logr) : 0.0;   // adv_n r_n
+    if (rowvalid && lr == 0) {
+      e.rowterms[4 * (size_t)row + 0] = ar;
+      e.rowterms[4 * (size_t)row + 1] = klt;
+      e.rowterms[4 * (size_t)row + 2] = ent;
+      e.rowterms[4 * (size_t)row + 3] = 0.0;
+    }
+    if constexpr (EPI == (int)RowEpi::kGaussPrepHead) {
+      // DS_L = -(adv r / N) z / sigma ; the rows of g_s: adv r (z^2 - 1)
+      const double coef = -ar * e.invN;
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        const float ds = real[t] ? (float)(coef * z[t] * c.is[t]) : 0.0f;
+        const float gs = real[t] ? (float)(ar * (z[t] * z[t] - 1.0)) : 0.0f;
+        if (st[t]) {
+          const size_t sidx = (size_t)row * e.ldo + 32 * t + lr;
+          e.out0[sidx] = real[t] ? mu[t] : 0.0f;
+          e.out1[sidx] = gs;
+          e.out2[sidx] = ds;
+          m2 = fmaxf(m2, fabsf(ds));
+        }
+      }
+    }
+  }
+}
+
 // Linear block id -> (m-tile, n-tile).  The n-tiles of one row tile are adjacent in
 // the swizzled order and land on one XCD (blocks b and b+8 share an XCD under the
 // observed round-robin dispatch: speed only, never correctness), so the second
@@ -397,16 +504,30 @@ __device__ __forceinline__ void row_epilogue(const RowGemmArgs& args, f32x16 (&a
   float mx0 = 0.0f, mx1 = 0.0f, mx2 = 0.0f;   // max |stored output| for the f16 operand scales
   if constexpr (epi_is_head(EPI)) {
     static_assert(WN == 1, "row-wise head epilogue needs the whole row in one wave half");
+    if constexpr (epi_is_gauss(EPI)) {
+      const GaussCols<TN> gc = gauss_cols<EPI, TN>(e, lr, args.N);
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
+      for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        float v[TN];
+        for (int r = 0; r < 16; ++r) {
+          const int row = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          float v[TN];
 #pragma unroll
-        for (int t = 0; t < TN; ++t) v[t] = acc[tm][t][r];
-        epi_row<EPI, TN>(e, row < M ? row : 0, row < M, lr, args.N, v, mx0, mx1, mx2);
-      }
+          for (int t = 0; t < TN; ++t) v[t] = acc[tm][t][r];
+          epi_row_gauss<EPI, TN>(e, gc, row < M ? row : 0, row < M, lr, args.N, v, mx0, mx2);
+        }
+    } else {
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          float v[TN];
+#pragma unroll
+          for (int t = 0; t < TN; ++t) v[t] = acc[tm][t][r];
+          epi_row<EPI, TN>(e, row < M ? row : 0, row < M, lr, args.N, v, mx0, mx1, mx2);
+        }
+    }
   } else {
     const bool fulln = (n0 + BN <= args.Npad);
     if (fulln) {

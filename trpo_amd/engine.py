@@ -19,6 +19,7 @@ from ._lib import MEM_DEVICE, MEM_HOST, check, lib
 __all__ = ["Engine", "UpdateParams", "ENVS", "env_info", "env_step_device"]
 
 _ADV_KINDS = {"returns": _lib.ADV_RETURNS, "gae": _lib.ADV_GAE}
+_DISTS = {"categorical": _lib.DIST_CATEGORICAL, "gaussian": _lib.DIST_GAUSSIAN}
 
 # the built-in environments of rollout.hip: name -> TRPO_ENV_* id
 ENVS = {"CartPole-v0": _lib.ENV_CARTPOLE_V0, "MountainCar-v0": _lib.ENV_MOUNTAINCAR_V0,
@@ -100,7 +101,12 @@ class UpdateParams:
 
 class Engine:
     def __init__(self, obs_dim: int, hidden: Sequence[int], n_actions: int, max_rows: int,
-                 device: int = 0):
+                 device: int = 0, dist: str = "categorical"):
+        """dist="categorical" is the reference's softmax policy over n_actions; dist="gaussian" a diagonal
+        Gaussian over n_actions action dimensions (include/trpo_engine.h, TRPO_DIST_GAUSSIAN): its feed is
+        set_batch_gaussian, its forward action_mean, its sampling act_gaussian."""
+        if dist not in _DISTS:
+            raise ValueError(f"Engine: dist must be one of {sorted(_DISTS)}, got {dist!r}")
         self.obs_dim = int(obs_dim)
         self.hidden = [int(h) for h in hidden]
         self.n_actions = int(n_actions)
@@ -108,8 +114,12 @@ class Engine:
         self.device = int(device)
         h = (ctypes.c_int * max(1, len(self.hidden)))(*self.hidden)
         handle = ctypes.c_void_p()
-        check(lib.trpo_create(ctypes.byref(handle), self.obs_dim, h, len(self.hidden), self.n_actions,
-                              self.max_rows, self.device), "trpo_create")
+        if dist == "categorical":
+            check(lib.trpo_create(ctypes.byref(handle), self.obs_dim, h, len(self.hidden), self.n_actions,
+                                  self.max_rows, self.device), "trpo_create")
+        else:
+            check(lib.trpo_create_dist(ctypes.byref(handle), _DISTS[dist], self.obs_dim, h, len(self.hidden),
+                                       self.n_actions, self.max_rows, self.device), "trpo_create_dist")
         self._h = handle
         self.num_params = int(lib.trpo_num_params(self._h))
         self.n = 0
@@ -135,6 +145,13 @@ class Engine:
 
     def synchronize(self):
         check(lib.trpo_synchronize(self._h), "trpo_synchronize")
+
+    @property
+    def dist(self) -> str:
+        """The policy's distribution family, as the engine reports it: "categorical" or "gaussian"."""
+        d = ctypes.c_int(0)
+        check(lib.trpo_get_dist(self._h, ctypes.byref(d)), "trpo_get_dist")
+        return {v: k for k, v in _DISTS.items()}[d.value]
 
     @property
     def stream_handle(self) -> int:
@@ -209,6 +226,25 @@ class Engine:
             raise ValueError("set_batch: pass all host arrays or all device tensors")
         check(lib.trpo_set_batch(self._h, n, n_global, s.ptr, a.ptr, adv.ptr, o.ptr, mems.pop()),
               "trpo_set_batch")
+        self.n, self.n_global = n, n_global
+        self._tail_ptr = None
+
+    def set_batch_gaussian(self, states, actions, advant, old_mean, old_logstd, n_global: Optional[int] = None):
+        """The Gaussian engine's feed: states [n, obs_dim], actions [n, A], advant [n] (or None), old_mean [n, A]
+        and old_logstd [A], float32; all host arrays or all device tensors."""
+        n = int(states.shape[0])
+        n_global = n if n_global is None else int(n_global)
+        A = self.n_actions
+        s = _Arg(states, np.float32, (n, self.obs_dim))
+        a = _Arg(actions, np.float32, (n, A))
+        adv = _Arg(advant, np.float32, (n,)) if advant is not None else _Arg(None, np.float32)
+        m = _Arg(old_mean, np.float32, (n, A))
+        ls = _Arg(old_logstd, np.float32, (A,))
+        mems = {x.mem for x in (s, a, m, ls, adv) if x.ptr is not None}
+        if len(mems) != 1:
+            raise ValueError("set_batch_gaussian: pass all host arrays or all device tensors")
+        check(lib.trpo_set_batch_gaussian(self._h, n, n_global, s.ptr, a.ptr, adv.ptr, m.ptr, ls.ptr, mems.pop()),
+              "trpo_set_batch_gaussian")
         self.n, self.n_global = n, n_global
         self._tail_ptr = None
 
@@ -308,6 +344,14 @@ class Engine:
         check(lib.trpo_action_dist(self._h, a.ptr, a.mem), "trpo_action_dist")
         return res
 
+    def action_mean(self):
+        """The Gaussian policy forward at the current parameters over the feed: (mean f32 [n, A], logstd f32 [A])."""
+        mean = np.empty((self.n, self.n_actions), np.float32)
+        logstd = np.empty(self.n_actions, np.float32)
+        check(lib.trpo_action_mean(self._h, mean.ctypes.data_as(ctypes.c_void_p),
+                                   logstd.ctypes.data_as(ctypes.c_void_p), MEM_HOST), "trpo_action_mean")
+        return mean, logstd
+
     def policy_grad(self, out=None):
         res, a = self._out(out, np.float32, self.num_params)
         check(lib.trpo_policy_grad(self._h, a.ptr, a.mem), "trpo_policy_grad")
@@ -366,6 +410,23 @@ class Engine:
         d = _Arg(dists, np.float32, writable=True)
         check(lib.trpo_act(self._h, s.ptr, n, u.ptr, int(bool(train)), a.ptr, d.ptr, s.mem), "trpo_act")
         return acts, dists
+
+    def act_gaussian(self, states, normals=None, train: bool = True):
+        """The Gaussian policy's act on a batch: (actions f32 [n, A], mean f32 [n, A], logstd f32 [A]) with
+        actions = float32(mean + exp(logstd) * normals), normals f64 [n, A] standard normals from the caller
+        (train=True), or actions = mean (train=False).  Host arrays."""
+        n = int(states.shape[0])
+        A = self.n_actions
+        s = _Arg(states, np.float32, (n, self.obs_dim))
+        xi = _Arg(normals, np.float64, (n, A)) if normals is not None else _Arg(None, np.float64)
+        if s.mem != MEM_HOST or (xi.ptr is not None and xi.mem != MEM_HOST):
+            raise ValueError("act_gaussian: host arrays expected")
+        acts, mean = np.empty((n, A), np.float32), np.empty((n, A), np.float32)
+        logstd = np.empty(A, np.float32)
+        ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        check(lib.trpo_act_gaussian(self._h, s.ptr, n, xi.ptr, int(bool(train)), ptr(acts), ptr(mean), ptr(logstd),
+                                    MEM_HOST), "trpo_act_gaussian")
+        return acts, mean, logstd
 
     def rollout_cartpole(self, n_envs: int = 1, n_timesteps: int = 1000, max_pathlength: int = 1000,
                          seed: int = 1, train: bool = True, time_limit: int = 200,
