@@ -277,3 +277,60 @@ def make_case(shape, seed=0, perturb=0.02, wide_sigma=False):
     if n > 1:
         adv = (adv - adv.mean()) / (adv.std() + 1e-8)
     return spec, theta, GaussBatch(X, actions, adv.astype(np.float32), old_mean, old_logstd)
+
+
+REGIMES = ("random", "tanh20", "mixed", "sigma_small", "sigma_spread")
+
+
+def make_hard_case(shape, regime, seed=0, perturb=0.02):
+    """make_case in the regimes where the engine's scaled f16 hi + lo split can fail (the constructions of
+    tests/test_gpu_fused16_hard.py and tests/test_gpu_rh1_planes.py) -> (spec, theta float32, GaussBatch):
+      random        as make_case;
+      tanh20        X *= 20: the first tanh layer saturated, 1 - H^2 near H's own rounding;
+      mixed         the last 3 rows of W_0 zero (theta and theta_old), rows 5, 34, 63, ... carry 2^15 N(0, 1) in
+                    those 3 features: X W_0 is exact, H_1 unsaturated, RH_1 2^15 larger on those rows;
+      sigma_small   logstd = -5 in every action dimension: 1/sigma^2 = e^10 in RD_L and DS_L;
+      sigma_spread  logstd = linspace(-4.5, 1.5, A): 1/sigma^2 spread by e^12 across the columns of RD_L and DS_L.
+    perturb = 0.02 is the loss / g / Hv feed, perturb = 0 the whole-update feed; the actions are sampled from the
+    old policy."""
+    if regime not in REGIMES:
+        raise ValueError(f"make_hard_case: regime must be one of {REGIMES}, got {regime!r}")
+    if regime == "random":
+        return make_case(shape, seed, perturb)
+    obs, hidden, A, n = shape
+    spec = GaussSpec(obs, list(hidden), A)
+    rng = np.random.RandomState(seed)
+    logstd = {"sigma_small": np.full(A, -5.0), "sigma_spread": np.linspace(-4.5, 1.5, A)}.get(regime)
+    theta = init_theta(spec, rng, logstd)
+    theta_old = (theta.astype(np.float64) * (1.0 + perturb * rng.standard_normal(theta.shape))).astype(np.float32)
+    X = rng.standard_normal((n, obs))
+    if regime == "tanh20":
+        X *= 20.0
+    elif regime == "mixed":
+        nz = min(3, obs)
+        for th in (theta, theta_old):
+            th[:obs * hidden[0]].reshape(obs, hidden[0])[obs - nz:, :] = 0.0
+        rows = np.arange(5, n, 29)
+        X[rows, obs - nz:] = 2.0 ** 15 * rng.standard_normal((rows.size, nz))
+    X = X.astype(np.float32)
+    old_logstd = theta_old[spec.n_net:].copy()
+    old_mean = mean_np(theta_old, X, spec).astype(np.float32)
+    actions = (old_mean.astype(np.float64)
+               + np.exp(old_logstd.astype(np.float64)) * rng.standard_normal((n, A))).astype(np.float32)
+    adv = rng.standard_normal(n)
+    if n > 1:
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    return spec, theta, GaussBatch(X, actions, adv.astype(np.float32), old_mean, old_logstd)
+
+
+def block_slices(spec):
+    """[(name, slice)] of the flat vector's parameter blocks: W0, b0, ..., WL, bL, logstd."""
+    w = spec.widths
+    out, off = [], 0
+    for i in range(len(w) - 1):
+        out.append((f"W{i}", slice(off, off + w[i] * w[i + 1])))
+        off += w[i] * w[i + 1]
+        out.append((f"b{i}", slice(off, off + w[i + 1])))
+        off += w[i + 1]
+    out.append(("logstd", slice(off, off + spec.act_dim)))
+    return out

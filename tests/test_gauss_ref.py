@@ -5,7 +5,10 @@ GPU.  CPU only.
 2. the float32 evaluation of the reference stays within 2.5e-6 of float64 on g and Hv (five shapes) and on
    stepdir, fullstep and theta of whole updates (the last four shapes), and within 2.5e-5 on kl: the GPU
    tests' 1e-5 bars, and their kl bar max(1e-5, 4 x this error) <= 1e-4, rest on these;
-3. the new calls are bound, and Engine(dist="gaussian") without a GPU fails with the usual error.
+3. the new calls are bound, and Engine(dist="gaussian") without a GPU fails with the usual error;
+4. the hard cases of tests/gauss_hard_cases.py (layer shapes, row counts, numerical regimes, the column reduction's
+   edges): make_hard_case builds each regime, the float32 reference is within 2.5e-6 per parameter block or within
+   2 x its recorded figure, float32 and float64 updates agree on cg_iters, k and reverted.
 
 (3, [8], 1, .) is left out of the whole updates on purpose: P = 41 is within reach of 10 CG iterations with
 residual_tol = 0, where float32 CG is off by 1e-2.
@@ -125,3 +128,171 @@ def test_gaussian_engine_creation_reports_errors():
     else:
         with Engine(3, [8], 1, max_rows=4, dist="gaussian") as e:
             assert e.dist == "gaussian" and e.num_params == 3 * 8 + 8 + 8 + 1 + 1
+
+
+# ---- the hard cases (tests/gauss_hard_cases.py): what the bars of tests/test_gpu_gauss_hard.py rest on ------------
+# The GPU bar of a quantity is max(1e-5, 4 x the float32 reference's own error on the same inputs).  Firm: the
+# float32 error is <= 2.5e-6 (kl: 2.5e-5, the bound of test_float32_reference_error_g_hv_kl), so the bar is 1e-5
+# (kl: at most 1e-4).  Every parameter block and every scalar is firm unless it is listed below with the figure
+# the committed seed gives; a listed one is held to 2 x its figure.  Why the listed ones are exceptions:
+#   sigma_small / sigma_spread g and the update built on it: a - mu is a float32 cancellation of order 6e-8 / sigma
+#     (the engine takes a and mu in float32 too); Hv does not read the actions and is firm;
+#   mixed: 2^15-sized features make the Fisher matrix ill-conditioned, ten float32 CG iterations leave float64's;
+#   C5 shapes: ten float32 CG iterations on 1.4M parameters from 300 rows;  (40, [17, 33], 2): 65 rows;
+#   tanh20 and n = 257 at 256 wide: 1 - H^2 near H's rounding, and a CG on it;
+#   colsum n = 1025: the tail entry is a sum of mean-zero terms that cancels.
+# The float32 sums follow the host's BLAS (its kernels and thread count), so another host gives other digits.
+import gauss_hard_cases as GH
+
+FIRM, FIRM_KL = 2.5e-6, 2.5e-5
+RECORDED = {
+    ("o40h17-33a2n65", "stepdir"): {"W2": 3.0e-06, "b2": 3.1e-06},
+    ("o40h17-33a2n65", "fullstep"): {"W2": 3.0e-06, "b2": 3.1e-06},
+    ("o17h256x2a6n515", "stepdir"): {"b2": 3.0e-06},
+    ("o17h256x2a6n515", "fullstep"): {"b2": 3.2e-06},
+    ("c5-n300", "stepdir"): {
+        "W0": 8.3e-06, "b0": 1.3e-04, "W1": 1.7e-05, "b1": 2.5e-04, "W2": 3.3e-05, "b2": 7.6e-04, "logstd": 2.7e-06,
+        "all": 2.2e-05},
+    ("c5-n300", "fullstep"): {
+        "W0": 8.4e-06, "b0": 1.3e-04, "W1": 1.7e-05, "b1": 2.5e-04, "W2": 3.3e-05, "b2": 7.6e-04, "logstd": 3.1e-06,
+        "all": 2.2e-05},
+    ("c4g-n257", "stepdir"): {
+        "W0": 2.5e-06, "b0": 2.7e-06, "W1": 2.8e-06, "b1": 3.8e-06, "W2": 3.2e-06, "b2": 2.6e-06, "logstd": 2.5e-06,
+        "all": 2.8e-06},
+    ("c4g-n257", "fullstep"): {
+        "W0": 2.5e-06, "b0": 2.7e-06, "W1": 2.8e-06, "b1": 3.8e-06, "W2": 3.2e-06, "b2": 2.6e-06, "logstd": 2.5e-06,
+        "all": 2.8e-06},
+    ("o17h64x2a6-tanh20", "g"): {"b2": 3.0e-06},
+    ("o17h64x2a6-mixed", "stepdir"): {
+        "W0": 3.0e-04, "b0": 4.0e-05, "W1": 4.2e-05, "b1": 3.9e-05, "W2": 4.2e-05, "b2": 3.9e-05, "logstd": 4.2e-05,
+        "all": 3.0e-04},
+    ("o17h64x2a6-mixed", "fullstep"): {
+        "W0": 3.1e-04, "b0": 2.8e-05, "W1": 2.5e-05, "b1": 2.9e-05, "W2": 2.5e-05, "b2": 2.9e-05, "logstd": 2.5e-05,
+        "all": 3.1e-04},
+    ("o17h64x2a6-mixed", "shs"): {"rel": 1.3e-04},
+    ("o17h64x2a6-mixed", "lm"): {"rel": 6.7e-05},
+    ("o17h64x2a6-mixed", "rate"): {"rel": 4.4e-06},
+    ("c4g-tanh20", "g"): {
+        "W0": 4.7e-06, "b0": 4.9e-06, "W1": 4.5e-06, "b1": 3.7e-06, "W2": 4.3e-06, "b2": 3.8e-06, "logstd": 4.5e-06,
+        "all": 4.6e-06},
+    ("c4g-tanh20", "Hv"): {"W0": 2.9e-06, "b0": 2.9e-06, "all": 2.6e-06},
+    ("c4g-tanh20", "stepdir"): {
+        "W0": 4.7e-06, "b0": 4.2e-06, "W1": 3.9e-06, "b1": 3.6e-06, "W2": 4.1e-06, "b2": 3.2e-06, "logstd": 2.8e-06,
+        "all": 4.4e-06},
+    ("c4g-tanh20", "fullstep"): {
+        "W0": 4.7e-06, "b0": 4.2e-06, "W1": 3.9e-06, "b1": 3.6e-06, "W2": 4.0e-06, "b2": 3.1e-06, "logstd": 2.8e-06,
+        "all": 4.3e-06},
+    ("c4g-mixed", "stepdir"): {
+        "W0": 2.1e-05, "b0": 2.4e-05, "W1": 2.5e-05, "b1": 2.4e-05, "W2": 2.4e-05, "b2": 2.4e-05, "logstd": 2.4e-05,
+        "all": 2.1e-05},
+    ("c4g-mixed", "fullstep"): {
+        "W0": 1.4e-05, "b0": 1.4e-05, "W1": 1.5e-05, "b1": 1.4e-05, "W2": 1.5e-05, "b2": 1.4e-05, "logstd": 1.4e-05,
+        "all": 1.4e-05},
+    ("c4g-mixed", "shs"): {"rel": 1.9e-05},
+    ("c4g-mixed", "lm"): {"rel": 9.5e-06},
+    ("c4g-mixed", "rate"): {"rel": 5.9e-06},
+    ("o17h64x2a6-sigma_small", "g"): {
+        "W0": 3.7e-05, "b0": 3.8e-05, "W1": 3.8e-05, "b1": 3.9e-05, "W2": 4.1e-05, "b2": 4.1e-05, "logstd": 3.3e-05,
+        "all": 3.9e-05},
+    ("o17h64x2a6-sigma_small", "stepdir"): {
+        "W0": 3.7e-05, "b0": 3.7e-05, "W1": 3.7e-05, "b1": 3.9e-05, "W2": 3.5e-05, "b2": 1.9e-05, "logstd": 5.2e-05,
+        "all": 3.7e-05},
+    ("o17h64x2a6-sigma_small", "fullstep"): {
+        "W0": 3.7e-05, "b0": 3.7e-05, "W1": 3.7e-05, "b1": 3.9e-05, "W2": 3.6e-05, "b2": 1.9e-05, "logstd": 5.3e-05,
+        "all": 3.7e-05},
+    ("c4g-sigma_spread", "g"): {
+        "W0": 1.7e-05, "b0": 1.8e-05, "W1": 1.7e-05, "b1": 1.8e-05, "W2": 1.7e-05, "b2": 1.8e-05, "logstd": 3.6e-05,
+        "all": 1.7e-05},
+    ("c4g-sigma_spread", "stepdir"): {
+        "W0": 2.6e-05, "b0": 2.6e-05, "W1": 2.5e-05, "b1": 2.3e-05, "W2": 2.5e-05, "b2": 2.6e-05, "logstd": 2.8e-05,
+        "all": 2.5e-05},
+    ("c4g-sigma_spread", "fullstep"): {
+        "W0": 2.6e-05, "b0": 2.6e-05, "W1": 2.5e-05, "b1": 2.3e-05, "W2": 2.5e-05, "b2": 2.6e-05, "logstd": 2.8e-05,
+        "all": 2.5e-05},
+    ("colsum-n1025", "g"): {"logstd": 7.8e-06},
+}
+
+
+def test_recorded_exceptions_name_cases_of_the_table():
+    assert {c for c, _ in RECORDED} <= set(GH.IDS)
+    firm = {"kl": FIRM_KL}
+    assert all(v >= firm.get(q, FIRM) for (_, q), blocks in RECORDED.items() for v in blocks.values())
+    # Hv is firm everywhere but under saturated tanh at 256 wide: it does not read the actions
+    assert [k for k in RECORDED if k[1] == "Hv"] == [("c4g-tanh20", "Hv")]
+
+
+@pytest.mark.parametrize("regime", GH.G.REGIMES)
+def test_make_hard_case_builds_the_regime(regime):
+    shape = (17, [64, 64], 6, 70)
+    for perturb in (0.02, 0.0):
+        spec, theta, b = G.make_hard_case(shape, regime, 7, perturb)
+        assert theta.dtype == b.X.dtype == b.actions.dtype == np.float32 and b.X.shape == (70, 17)
+        W0 = theta[:17 * 64].reshape(17, 64)
+        s = theta[spec.n_net:]
+        if perturb == 0.0:
+            assert np.array_equal(b.old_logstd, s)
+            assert np.array_equal(b.old_mean, G.mean_np(theta, b.X, spec).astype(np.float32))
+        if regime == "random":
+            ref = G.make_case(shape, 7, perturb)
+            assert np.array_equal(theta, ref[1]) and np.array_equal(b.X, ref[2].X)
+            assert np.array_equal(b.actions, ref[2].actions)
+        elif regime == "tanh20":
+            h1 = np.tanh(b.X.astype(np.float64) @ W0 + theta[17 * 64:17 * 64 + 64])
+            assert (1 - h1 * h1 < 1e-6).mean() > 0.5
+        elif regime == "mixed":
+            rows = np.arange(5, 70, 29)
+            assert list(rows) == [5, 34, 63]
+            assert not W0[-3:].any() and W0[:-3].all()
+            big = np.zeros(70, bool)
+            big[rows] = True
+            assert np.abs(b.X[big, -3:]).max() > 2.0 ** 14 and np.abs(b.X[~big]).max() < 8
+            assert np.abs(b.X[big, :-3]).max() < 8
+            # theta_old has the zero rows too: the old mean does not see the large features
+            assert np.abs(b.old_mean).max() < 50 and np.all(np.isfinite(b.actions))
+            X0 = b.X.copy()
+            X0[:, -3:] = 0
+            assert np.array_equal(G.mean_np(theta, X0, spec), G.mean_np(theta, b.X, spec))
+        elif regime == "sigma_small":
+            assert np.array_equal(s, np.full(6, -5.0, np.float32))
+        else:
+            assert np.array_equal(s, np.linspace(-4.5, 1.5, 6).astype(np.float32))
+            assert 2 * (s[-1] - s[0]) == 12.0
+    with pytest.raises(ValueError, match="regime must be one of"):
+        G.make_hard_case(shape, "head25", 7)
+
+
+@pytest.mark.parametrize("case", GH.IDS)
+def test_float32_reference_error_hard_cases(case):
+    """Every quantity of every hard case in float32 against float64, per parameter block: firm, or within 2 x its
+    recorded figure; float32 and float64 updates agree on cg_iters, k and reverted."""
+    errs = GH.float32_errors(case)
+    for q, blocks in errs.items():
+        print(f"{case} {q}: " + "  ".join(f"{name} {e:.2e}" for name, e in blocks.items()))
+    if "update" in GH.BY_ID[case].checks:
+        r64, r32 = GH.update_refs(case)
+        print(f"{case} update: cg_iters {r64.cg_iters}/{r32.cg_iters} k {r64.k}/{r32.k} reverted "
+              f"{r64.reverted}/{r32.reverted}")
+        assert r32.stepdir.dtype == np.float32 and r64.stepdir.dtype == np.float64
+        assert (r32.cg_iters, r32.k, r32.reverted) == (r64.cg_iters, r64.k, r64.reverted)
+        assert r64.cg_iters == 10 and not r64.reverted
+    for q, blocks in errs.items():
+        firm = FIRM_KL if q == "kl" else FIRM
+        for name, e in blocks.items():
+            bound = max(firm, 2.0 * RECORDED.get((case, q), {}).get(name, 0.0))
+            assert e <= bound, f"{case} {q} {name}: float32 error {e:.3e} > {bound:.1e}"
+
+
+def test_sigma_spread_hv_columns_float32():
+    """The float32 reference per column of W_L's Hv block under sigma_spread: each column against its own norm is
+    far inside 2.5e-6, so the GPU test's column-by-column bar is firm at 1e-5."""
+    case = "c4g-sigma_spread"
+    spec, _, _ = GH.feed(case)
+    hv64, hv32 = GH.vec_refs(case)["hv"]
+    sl = dict(G.block_slices(spec))[f"W{len(spec.hidden)}"]
+    c64, c32 = (h[sl].reshape(spec.hidden[-1], spec.act_dim) for h in (hv64, hv32))
+    errs = [rel_l2(c32[:, j], c64[:, j]) for j in range(spec.act_dim)]
+    norms = np.linalg.norm(c64, axis=0)
+    print(f"{case} Hv W_L columns: worst float32 error {max(errs):.2e}; column norms {norms.max():.2e} .. "
+          f"{norms.min():.2e}")
+    assert max(errs) <= 1e-6
+    assert norms.max() / norms.min() > 2.0 ** 15      # the regime: the small columns are below 2^-15 of the block's max

@@ -1,7 +1,7 @@
 """Several ranks on the visible GPU(s): the engine's multi-rank update vs a single-rank engine.
 
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29555 \
-        tools/mrank_check.py [--host-allreduce] [--dims c3|c4|c5] [--rows N] [--graphs]
+        tools/mrank_check.py [--host-allreduce] [--dims c3|c4|c5|g17] [--dist gaussian] [--rows N] [--graphs]
 
 --host-allreduce  ranks share a GPU (RCCL refuses duplicate devices): the engine's all-reduces run
                   through its stream-ordered host transport, summed by gloo on the host
@@ -9,6 +9,10 @@
 --dims c5         obs 376, 1024x1024, 17 actions (BASELINE configs[4]'s layer shapes)
 --graphs          also replay the update as a captured hipGraph (all-reduces inside it) and require
                   every replay to be bitwise identical to the eager update
+--dist gaussian   a diagonal-Gaussian engine (set_batch_gaussian with the advantages given directly): --dims g17
+                  is (17, [64, 64], 6) and c4 is read as (128, [256, 256], 17); the cut between the ranks is uneven
+                  (shard_bounds moved to the next multiple of 173 rows); stepdir is held to 1e-5 too, and the
+                  log-std tail of Hv, theta and stepdir also on its own
 Checks: ranks bitwise identical; Hv and theta within 1e-5 of one rank holding all rows; same k.
 """
 import argparse
@@ -19,7 +23,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-DIMS = {"c3": (128, [64, 64], 18), "c4": (128, [256, 256], 18), "c5": (376, [1024, 1024], 17)}
+DIMS = {"c3": (128, [64, 64], 18), "c4": (128, [256, 256], 18), "c5": (376, [1024, 1024], 17),
+        "g17": (17, [64, 64], 6)}
+GAUSS_DIMS = {"g17": DIMS["g17"], "c4": (128, [256, 256], 17)}
 
 
 def main():
@@ -28,7 +34,11 @@ def main():
     ap.add_argument("--dims", default="c3", choices=sorted(DIMS))
     ap.add_argument("--rows", type=int, default=40_000)
     ap.add_argument("--graphs", action="store_true")
+    ap.add_argument("--dist", default="categorical", choices=["categorical", "gaussian"])
     args = ap.parse_args()
+    gauss = args.dist == "gaussian"
+    if gauss != (args.dims == "g17") and args.dims != "c4":
+        ap.error(f"--dims {args.dims} does not go with --dist {args.dist}")
 
     import torch
     import torch.distributed as dist
@@ -41,39 +51,65 @@ def main():
     dev = local % max(1, ndev)
     torch.cuda.set_device(dev)
     from trpo_amd import Engine, UpdateParams
-    from trpo_amd._lib import get_option, set_option
+    from trpo_amd._lib import VEC_STEPDIR, get_option, set_option
     from trpo_amd.dist import init_engine_comm, shard_bounds
     from oracle import trpo_oracle as O
-    obs, hidden, A = DIMS[args.dims]
-    spec = O.PolicySpec(obs, hidden, A)
     n = args.rows
-    d = O.synthetic_batch(spec, n, seed=3, episode_len=200)
-    lo, hi = shard_bounds(n, world, d["starts"])[rank]
-    e = Engine(spec.obs_dim, spec.hidden, spec.n_actions, max_rows=hi - lo, device=dev)
+    if gauss:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import gauss_ref as G
+        obs, hidden, A = GAUSS_DIMS[args.dims]
+        # theta_old = theta: the whole-update feed, the advantages given directly (standardised over all rows)
+        spec, theta, gb = G.make_case((obs, hidden, A, n), seed=3, perturb=0.0)
+        starts = (np.arange(n) % 173 == 0).astype(np.uint8)    # an uneven cut: the next multiple of 173 rows
+        prm = UpdateParams(residual_tol=0.0)
+
+        def new_engine(rows):
+            return Engine(obs, hidden, A, max_rows=rows, device=dev, dist="gaussian")
+
+        def feed(e, lo, hi):
+            e.set_flat(theta)
+            e.set_batch_gaussian(gb.X[lo:hi], gb.actions[lo:hi], gb.advant[lo:hi], gb.old_mean[lo:hi], gb.old_logstd,
+                                 n_global=n)
+    else:
+        obs, hidden, A = DIMS[args.dims]
+        spec = O.PolicySpec(obs, hidden, A)
+        d = O.synthetic_batch(spec, n, seed=3, episode_len=200)
+        theta, starts = d["theta"], d["starts"]
+        prm = UpdateParams(residual_tol=0.0, compute_advantages=True)
+
+        def new_engine(rows):
+            return Engine(spec.obs_dim, spec.hidden, spec.n_actions, max_rows=rows, device=dev)
+
+        def feed(e, lo, hi):
+            e.set_flat(theta)
+            e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], None, d["old_dist"][lo:hi], n_global=n)
+            e.set_rewards(d["rewards"][lo:hi], d["starts"][lo:hi])
+            e.compute_advantages(0.95)
+    lo, hi = shard_bounds(n, world, starts)[rank]
+    assert 0 <= lo < hi <= n, f"rank {rank}: empty shard [{lo}, {hi})"
+    e = new_engine(hi - lo)
     if args.host_allreduce:
         def ar(arr):
             dist.all_reduce(torch.from_numpy(arr))
         e.comm_set_host_allreduce(ar, rank, world)
     else:
         init_engine_comm(e, rank, world)
-    e.set_flat(d["theta"])
-    e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], None, d["old_dist"][lo:hi], n_global=n)
-    e.set_rewards(d["rewards"][lo:hi], d["starts"][lo:hi])
+    feed(e, lo, hi)
     v = np.random.RandomState(1).standard_normal(spec.n_params).astype(np.float32)
-    e.compute_advantages(0.95)
     hv = e.fvp(v, 0.0)
-    prm = UpdateParams(residual_tol=0.0, compute_advantages=True)
     saved = get_option("graphs")
     set_option("graphs", 0)
     st = e.update(prm)
     th = e.get_flat()
+    sd = e.get_vector(VEC_STEPDIR)
     replays = []
     if args.graphs:
         # graphs on: the 1st update with this key runs eagerly, the 2nd captures and launches,
         # the 3rd and 4th replay
         set_option("graphs", 1)
         for _ in range(4):
-            e.set_flat(d["theta"])
+            e.set_flat(theta)
             stg = e.update(prm)
             replays.append((stg, e.get_flat()))
     set_option("graphs", saved)
@@ -86,11 +122,8 @@ def main():
     if rank == 0:
         for t in allth[1:]:
             assert np.array_equal(t, allth[0]), "ranks diverged"
-        e1 = Engine(spec.obs_dim, spec.hidden, spec.n_actions, max_rows=n, device=dev)
-        e1.set_flat(d["theta"])
-        e1.set_batch(d["X"], d["actions"], None, d["old_dist"])
-        e1.set_rewards(d["rewards"], d["starts"])
-        e1.compute_advantages(0.95)
+        e1 = new_engine(n)
+        feed(e1, 0, n)
         hv1 = e1.fvp(v, 0.0)
         st1 = e1.update(prm)
         th1 = e1.get_flat()
@@ -100,6 +133,15 @@ def main():
               f"k={st['k']}/{st1['k']} iters={st['cg_iters']}/{st1['cg_iters']} graph replays={len(replays)}",
               flush=True)
         assert r1 < 1e-5 and r2 < 1e-5 and st["k"] == st1["k"]
+        if gauss:
+            t1 = np.linalg.norm(hv[-A:] - hv1[-A:]) / np.linalg.norm(hv1[-A:])
+            t2 = np.linalg.norm(th[-A:] - th1[-A:]) / np.linalg.norm(th1[-A:])
+            sd1 = e1.get_vector(VEC_STEPDIR)
+            t3 = np.linalg.norm(sd - sd1) / np.linalg.norm(sd1)     # theta hides the step behind theta_0
+            t4 = np.linalg.norm(sd[-A:] - sd1[-A:]) / np.linalg.norm(sd1[-A:])
+            print(f"dist=gaussian shards {shard_bounds(n, world, starts)} FVP rel {r1:.2e} theta rel {r2:.2e}; "
+                  f"log-std tail: FVP rel {t1:.2e} theta rel {t2:.2e}; stepdir rel {t3:.2e} (tail {t4:.2e})", flush=True)
+            assert t1 < 1e-5 and t2 < 1e-5 and t3 < 1e-5 and t4 < 1e-5
         print("MRANK OK", flush=True)
     dist.barrier()
     dist.destroy_process_group()
