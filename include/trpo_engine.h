@@ -118,9 +118,11 @@ int trpo_create(trpo_engine** out, int obs_dim, const int* hidden, int n_hidden,
  * trpo_update, trpo_get/set_flat, trpo_get_vector, trpo_set_rewards, trpo_compute_advantages, the
  * estimator, tail-value and baseline calls, trpo_explained_variance, trpo_get_feed_view (whose old_dist
  * then points at old_mean and n_actions is act_dim), the comm calls and profiling work unchanged.  The
- * categorical-only calls (trpo_set_batch, trpo_action_dist, trpo_act, trpo_rollout_* and
- * trpo_rollout_to_batch) on a Gaussian engine, and the three Gaussian calls on a categorical engine, return
- * TRPO_ERR_STATE with a message that names the engine's distribution; nothing is launched. */
+ * categorical-only calls (trpo_set_batch, trpo_action_dist, trpo_act, trpo_rollout_env, trpo_rollout_cartpole,
+ * trpo_rollout_fetch*, and trpo_rollout_to_batch) on a Gaussian engine, and the Gaussian calls
+ * (trpo_set_batch_gaussian, trpo_action_mean, trpo_act_gaussian and the four trpo_rollout_gaussian* calls) on a
+ * categorical engine, return TRPO_ERR_STATE with a message that names the engine's distribution; nothing is
+ * launched.  A Gaussian engine rolls out the continuous-action environments (trpo_rollout_gaussian, below). */
 #define TRPO_DIST_CATEGORICAL 0
 #define TRPO_DIST_GAUSSIAN 1
 /* trpo_create for either family; act_dim <= 128 (trpo_act_gaussian: <= 64) */
@@ -489,6 +491,75 @@ int trpo_cartpole_step(const double* state, const int64_t* action, int64_t n, do
  * any output may be NULL.  Engine-free, current device. */
 int trpo_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out, double* obs_out,
                   double* reward, uint8_t* done, int mem);
+
+/* ==== continuous-action rollouts under the Gaussian policy ======================================
+ * Two of gym's continuous-action classic_control tasks roll out on a TRPO_DIST_GAUSSIAN engine the way the
+ * discrete ones do on a categorical engine: one wave per environment, whole episodes until the environment's own
+ * step count reaches ceil(n_timesteps / n_envs), the path-end records, the concatenation in environment order.
+ * They have a table and entry points of their own, next to the discrete ones.  gym is not vendored: the equations
+ * below are the definition.  All arithmetic is float64 in the operation order written (x^2 is x*x),
+ * pi = 3.141592653589793, clamp(x, lo, hi) = min(max(x, lo), hi) as Python's; an action component is the float32
+ * the policy produced, widened to float64.
+ *
+ * Pendulum-v1: state (th, thd); obs (cos th, sin th, thd); act_dim 1; time limit 200; it never terminates.
+ *   reset: th = -pi + (pi - -pi)*u0, thd = -1 + (1 - -1)*u1 (two draws)
+ *   step:  u = clamp(a, -2, 2);  y = th + pi;  m = fmod(y, 2*pi);  if (m < 0) m = m + 2*pi;  an = m - pi
+ *          cost = an*an + 0.1*(thd*thd) + 0.001*(u*u)
+ *          thd' = thd + (3*10.0/(2*1.0)*sin(th) + 3.0/(1.0*(1.0*1.0))*u)*0.05;  thd' = clamp(thd', -8, 8)
+ *          th' = th + thd'*0.05;  reward = -cost;  done = false
+ * MountainCarContinuous-v0: state = obs = (p, v); act_dim 1; time limit 999.
+ *   reset: p = -0.6 + (-0.4 - -0.6)*u0, v = 0 (one draw)
+ *   step:  f = clamp(a, -1, 1);  v = v + f*0.0015 + cos(3*p)*(-0.0025);  v = clamp(v, -0.07, 0.07)
+ *          p = p + v;  p = clamp(p, -1.2, 0.6);  if (p == -1.2 && v < 0) v = 0
+ *          done = p >= 0.45 && v >= 0;  reward = (done ? 100 : 0) - (a*a)*0.1, with the unclamped a, as gym's
+ *
+ * Per step the rollout runs the policy's mean forward on float32(obs) and forms, for d < act_dim,
+ * a_d = float32(double(mu_d) + exp(double(logstd_d)) * xi_d) when train (trpo_act_gaussian's arithmetic), else
+ * a_d = mu_d with a recorded xi of 0.  The normals are a Box-Muller pair off one Philox call: counter (env index,
+ * stream 0, k) with k = step_count*act_dim + d, step_count the environment's steps so far over all its episodes
+ * (it advances whether or not train); u1 from words (c0, c1) and u2 from (c2, c3) by the 53-bit recipe
+ * ((c>>5)*2^26 + (c'>>6)) / 2^53; xi = sqrt(-2*log(1 - u1)) * cos(2*pi*u2).  Reset draws are as for the discrete
+ * environments: stream 1, index episode*reset_draws + i.  The rollout samples with a snapshot of the log-std
+ * vector taken when it starts. */
+#define TRPO_CENV_PENDULUM_V1 0
+#define TRPO_CENV_MOUNTAINCAR_CONTINUOUS_V0 1
+typedef struct trpo_cont_env_info_t {
+  int obs_dim, state_dim, act_dim;
+  int reset_draws;           /* uniforms one env.reset() consumes */
+  int time_limit;            /* the task's TimeLimit */
+  char name[32];
+} trpo_cont_env_info_t;
+/* Host-only (works with no GPU): the table of a continuous-action environment; an unknown id is TRPO_ERR_ARG. */
+int trpo_cont_env_info(int cenv, trpo_cont_env_info_t* out);
+/* trpo_default_rollout_params with the environment's own time_limit */
+int trpo_default_rollout_params_cont(int cenv, trpo_rollout_params* p);
+/* The rollout of environment `cenv` (TRPO_CENV_*) on a Gaussian engine whose obs_dim and act_dim are the
+ * environment's: TRPO_ERR_ARG otherwise, with both in the message.  In `p`, train = 1 samples and train = 0 acts
+ * with the mean; the injected action_uniforms are standard normals [n_envs][ceil(n_timesteps/n_envs) +
+ * min(max_pathlength, time_limit) - 1][act_dim].  Returns the total steps N and the number of paths. */
+int trpo_rollout_gaussian(trpo_engine* e, int cenv, const trpo_rollout_params* p, int64_t* n_steps_out,
+                          int64_t* n_paths_out);
+/* the concatenated paths: obs [N][obs_dim] f64 (and/or f32), actions and means [N][act_dim] f32, logstd [act_dim]
+ * f32 (the rollout's snapshot), rewards [N] f64, episode_starts [N] u8, the normal of every action component
+ * [N][act_dim] f64 (zeros when train = 0) and the state every observation was made from [N][state_dim] f64; any
+ * may be NULL */
+int trpo_rollout_gaussian_fetch(trpo_engine* e, double* obs, float* obs32, float* actions, float* means,
+                                float* logstd, double* rewards, uint8_t* episode_starts, double* normals,
+                                double* env_states, int mem);
+/* trpo_rollout_fetch_ends of a Gaussian rollout: final_means [n_paths][act_dim] f32 is the policy's mean at
+ * float32(s_T) for cut-off paths, zeros for terminated ones */
+int trpo_rollout_gaussian_fetch_ends(trpo_engine* e, uint8_t* truncated, double* final_obs, float* final_means,
+                                     int64_t* lengths, int64_t* end_rows, int mem);
+/* the rollout becomes the feed on the device: states, actions, old mean, the old log-std from the rollout's
+ * snapshot, rewards, path starts and the path-end records; baseline and tail values cleared.  trpo_get_feed_view,
+ * trpo_get_tail_view (final_dist = the mean at s_T, n_actions = act_dim), trpo_vf_predict_tails,
+ * trpo_compute_advantages and trpo_update then work as on a categorical rollout feed. */
+int trpo_rollout_gaussian_to_batch(trpo_engine* e, int64_t n_global);
+/* one step per row of environment `cenv`: state [n][state_dim] f64, action [n][act_dim] f32 -> state_out, obs_out
+ * [n][obs_dim] (the observation of state_out), reward [n], done [n] (termination, not the TimeLimit); any output
+ * may be NULL.  Engine-free, current device. */
+int trpo_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
+                       double* obs_out, double* reward, uint8_t* done, int mem);
 
 /* ==== value-function baseline: class VF (utils.py:48-92) ==================================
  * Features [obs | action_dist | t/10] (VF._features, utils.py:70-77) -> fully_connected(64, relu)

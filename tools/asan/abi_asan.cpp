@@ -110,6 +110,27 @@ int main() {
   CHECK_ERR(trpo_env_step(TRPO_ENV_ACROBOT_V1, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST),
             TRPO_ERR_ARG);
   CHECK_ERR(trpo_rollout_to_batch(nullptr, 1), TRPO_ERR_ARG);
+  // the continuous-action family: its host-only table, and NULL engines
+  trpo_cont_env_info_t ci;
+  CHECK(trpo_cont_env_info(TRPO_CENV_PENDULUM_V1, &ci) == TRPO_OK && ci.obs_dim == 3 && ci.state_dim == 2 &&
+        ci.act_dim == 1 && ci.reset_draws == 2 && ci.time_limit == 200 && std::string(ci.name) == "Pendulum-v1");
+  CHECK(trpo_cont_env_info(TRPO_CENV_MOUNTAINCAR_CONTINUOUS_V0, &ci) == TRPO_OK && ci.obs_dim == 2 &&
+        ci.time_limit == 999 && std::string(ci.name) == "MountainCarContinuous-v0");
+  CHECK_ERR(trpo_cont_env_info(2, &ci), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_cont_env_info(TRPO_CENV_PENDULUM_V1, nullptr), TRPO_ERR_ARG);
+  CHECK(trpo_default_rollout_params_cont(TRPO_CENV_MOUNTAINCAR_CONTINUOUS_V0, &rp) == TRPO_OK && rp.time_limit == 999);
+  CHECK_ERR(trpo_default_rollout_params_cont(-1, &rp), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_default_rollout_params_cont(TRPO_CENV_PENDULUM_V1, nullptr), TRPO_ERR_ARG);
+  trpo_default_rollout_params(&rp);
+  CHECK_ERR(trpo_cont_env_step(2, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_cont_env_step(TRPO_CENV_PENDULUM_V1, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr,
+                               TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_gaussian(nullptr, TRPO_CENV_PENDULUM_V1, &rp, nullptr, nullptr), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_gaussian_fetch(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                        nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_gaussian_fetch_ends(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST),
+            TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_gaussian_to_batch(nullptr, 1), TRPO_ERR_ARG);
   trpo_feed_view fv;
   CHECK_ERR(trpo_get_feed_view(nullptr, &fv), TRPO_ERR_ARG);
   double ev = 0.0;

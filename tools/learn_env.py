@@ -1,10 +1,11 @@
 """Run learn() (the reference's loop, trpo_inksci.py:89-177) on one of the built-in environments on the GPU and
 print the reference's per-iteration statistics.
 usage: python tools/learn_env.py ENV iterations n_envs [gae_lambda] [bootstrap]
-ENV is CartPole-v0, MountainCar-v0 or Acrobot-v1 (trpo_amd.engine.ENVS).  gae_lambda given: GAE(lambda) advantages
+ENV is CartPole-v0, MountainCar-v0 or Acrobot-v1 (trpo_amd.engine.ENVS), or a continuous-action environment under a
+diagonal-Gaussian policy: Pendulum-v1 or MountainCarContinuous-v0 (trpo_amd.engine.CONT_ENVS).  gae_lambda given: GAE(lambda) advantages
 instead of the reference's discount(rewards) - baseline; the word "bootstrap" after it: paths cut off by the time
 limit are bootstrapped from V(s_T).  Training stops at the reference's mean episode reward of 1.1*500 on
-CartPole-v0; the other two, whose rewards are never positive, train for all the iterations asked for."""
+CartPole-v0; the others, whose mean episode rewards stay below it, train for all the iterations asked for."""
 import os
 import sys
 import time
@@ -13,9 +14,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from trpo_amd import TRPOAgent  # noqa: E402
 from trpo_amd.agent import CONFIG  # noqa: E402
-from trpo_amd.engine import ENVS, env_info  # noqa: E402
+from trpo_amd.engine import CONT_ENVS, ENVS, cont_env_info, env_info  # noqa: E402
 
-if len(sys.argv) < 4 or sys.argv[1] not in ENVS:
+if len(sys.argv) < 4 or (sys.argv[1] not in ENVS and sys.argv[1] not in CONT_ENVS):
     sys.exit(__doc__)
 env = sys.argv[1]
 iters, n_envs = int(sys.argv[2]), int(sys.argv[3])
@@ -23,7 +24,11 @@ gae_lambda = float(sys.argv[4]) if len(sys.argv) > 4 else None
 bootstrap = len(sys.argv) > 5
 if bootstrap and sys.argv[5] != "bootstrap":
     sys.exit(f"unknown fifth argument {sys.argv[5]!r}: expected 'bootstrap'")
-info = env_info(env)
+if env in CONT_ENVS:
+    info = cont_env_info(env)
+    info["n_actions"] = info["act_dim"]
+else:
+    info = env_info(env)
 config = {**CONFIG, "env": env, "gae_lambda": gae_lambda}
 if bootstrap:
     config["bootstrap_truncated"] = True

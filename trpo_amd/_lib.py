@@ -54,6 +54,14 @@ class EnvInfo(ctypes.Structure):
                 ("time_limit", c_int), ("name", ctypes.c_char * 32)]
 
 
+CENV_PENDULUM_V1, CENV_MOUNTAINCAR_CONTINUOUS_V0 = range(2)
+
+
+class ContEnvInfo(ctypes.Structure):
+    _fields_ = [("obs_dim", c_int), ("state_dim", c_int), ("act_dim", c_int), ("reset_draws", c_int),
+                ("time_limit", c_int), ("name", ctypes.c_char * 32)]
+
+
 class CommInfo(ctypes.Structure):
     _fields_ = [("transport", c_int), ("rank", c_int), ("world", c_int), ("comm_count", c_int),
                 ("comm_rank", c_int), ("comm_device", c_int), ("device", c_int), ("pci_bus_id", ctypes.c_char * 64)]
@@ -146,6 +154,16 @@ SIGNATURES = {
     "trpo_act_gaussian": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "trpo_cat_sample": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int]),
     "trpo_cartpole_step": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int]),
+    # continuous-action rollouts under the Gaussian policy
+    "trpo_cont_env_info": (c_int, [c_int, POINTER(ContEnvInfo)]),
+    "trpo_default_rollout_params_cont": (c_int, [c_int, POINTER(RolloutParams)]),
+    "trpo_rollout_gaussian": (c_int, [c_void_p, c_int, POINTER(RolloutParams), POINTER(c_int64), POINTER(c_int64)]),
+    "trpo_rollout_gaussian_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_int]),
+    "trpo_rollout_gaussian_fetch_ends": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "trpo_rollout_gaussian_to_batch": (c_int, [c_void_p, c_int64]),
+    "trpo_cont_env_step": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int]),
     # value-function baseline (utils.py:48-92)
     "trpo_vf_create": (c_int, [POINTER(c_void_p), c_int, POINTER(c_int), c_int, c_int64, c_int]),
     "trpo_vf_destroy": (None, [c_void_p]),

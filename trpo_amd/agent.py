@@ -34,7 +34,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .engine import Engine, UpdateParams, env_info
+from .engine import CONT_ENVS, Engine, UpdateParams, cont_env_info, env_info
 from .vf import VF
 from .utils import (EngineLoss, GetFlat, KLFirstFixedGVP, SetFromFlat, SurrogateLoss, conjugate_gradient,
                     flatgrad, linesearch)
@@ -47,6 +47,10 @@ CONFIG = {"max_steps": 1000, "episodes_per_roll": 1000, "gamma": 0.95, "cg_dampi
 # Two more optional keys, neither in the reference: "env" (default "CartPole-v0"), the built-in environment
 # learn() rolls out (trpo_amd.engine.ENVS), and "reward_target" (default the reference's 1.1*500), the mean
 # episode reward above which learn() stops training.
+# "env" may also name a continuous-action environment (trpo_amd.engine.CONT_ENVS: Pendulum-v1,
+# MountainCarContinuous-v0): the agent then builds a diagonal-Gaussian engine, its second argument counts action
+# dimensions, "init_logstd" (default 0.0) is the initial log-std of every one, the paths feed() / update() take are
+# Gaussian paths (gaussian_paths_to_batch) and learn() rolls out with Engine.rollout_gaussian.
 DEFAULT_ENV = "CartPole-v0"
 REWARD_TARGET = 1.1 * 500   # trpo_inksci.py:135
 
@@ -55,18 +59,27 @@ class Session:
     """Stands in for the ``tf.Session`` the reference threads through utils (trpo_inksci.py:23)."""
 
     def __init__(self, engine: Engine, init_rng: Optional[np.random.RandomState] = None,
-                 reinit_policy: bool = True):
+                 reinit_policy: bool = True, init_logstd: Optional[float] = None):
         self.engine = engine
         self.init_rng = init_rng or np.random.RandomState(1)
         self.reinit_policy = reinit_policy
+        self.init_logstd = init_logstd     # a Gaussian engine's log-std tail; None: a categorical engine
+
+    def draw_theta(self) -> np.ndarray:
+        """A fresh initialisation of the engine's flat parameters: xavier_theta, then on a Gaussian engine the
+        log-std tail at init_logstd."""
+        e = self.engine
+        theta = xavier_theta(e.obs_dim, e.hidden, e.n_actions, self.init_rng)
+        if self.init_logstd is None:
+            return theta
+        return np.concatenate([theta, np.full(e.n_actions, self.init_logstd, np.float32)])
 
     def initialize_all_variables(self):
         """tf.initialize_all_variables() re-draws every variable, the policy included; the reference
         runs it again when the VF creates its net (utils.py:66), so its first update starts from a
         fresh initialisation.  reinit_policy=False keeps the current policy instead."""
         if self.reinit_policy:
-            e = self.engine
-            self.engine.set_flat(xavier_theta(e.obs_dim, e.hidden, e.n_actions, self.init_rng))
+            self.engine.set_flat(self.draw_theta())
 
 
 def xavier_theta(obs_dim: int, hidden: Sequence[int], n_actions: int,
@@ -112,6 +125,41 @@ def paths_to_batch(paths: List[Dict]) -> Dict[str, np.ndarray]:
     return out
 
 
+def gaussian_paths_to_batch(paths: List[Dict]) -> Dict[str, np.ndarray]:
+    """paths_to_batch for a Gaussian policy's paths: dicts with obs, actions [T][A] f32, action_means [T][A], logstd
+    [A] (one vector for the whole batch: the old policy's), rewards and optional baseline / tail_value."""
+    T = [len(p["rewards"]) for p in paths]
+    logstd = np.asarray(paths[0]["logstd"], np.float32).reshape(-1)
+    A = logstd.shape[0]
+    for p in paths[1:]:
+        if not np.array_equal(np.asarray(p["logstd"], np.float32).reshape(-1), logstd):
+            raise ValueError("the paths of one batch must share their logstd (one old policy)")
+    starts = []
+    for t in T:
+        s = np.zeros(t, np.uint8)
+        s[0] = 1
+        starts.append(s)
+    out = {
+        "state": np.concatenate([np.asarray(p["obs"], np.float32).reshape(t, -1) for p, t in zip(paths, T)]),
+        "action": np.concatenate([np.asarray(p["actions"], np.float32).reshape(t, A) for p, t in zip(paths, T)]),
+        "action_mean": np.concatenate([np.asarray(p["action_means"], np.float32).reshape(t, A)
+                                       for p, t in zip(paths, T)]),
+        "logstd": logstd,
+        "rewards": np.concatenate([np.asarray(p["rewards"], np.float64) for p in paths]),
+        "baseline": np.concatenate([np.asarray(p.get("baseline", np.zeros(t)), np.float64)
+                                    for p, t in zip(paths, T)]),
+        "starts": np.concatenate(starts),
+    }
+    if any("tail_value" in p for p in paths):
+        tails = []
+        for p, t in zip(paths, T):
+            tv = np.zeros(t, np.float64)
+            tv[-1] = float(p.get("tail_value", 0.0))
+            tails.append(tv)
+        out["tail_values"] = np.concatenate(tails)
+    return out
+
+
 def rollout_seed(seed: int, iteration: int, rank: int) -> int:
     """The Philox key of one rank's rollout at one iteration: ranks live 2^40 keys apart, so no rank
     ever draws another rank's stream at any reachable iteration count."""
@@ -128,23 +176,33 @@ class TRPOAgent:
             raise ValueError("config['bootstrap_truncated'] needs config['gae_lambda']: the reference's "
                              "returns - baseline estimator takes no tail values")
         self.env = self.config.get("env", DEFAULT_ENV)
-        self.env_info = env_info(self.env)
+        # a continuous-action environment (trpo_amd.engine.CONT_ENVS) makes the policy a diagonal Gaussian over
+        # its act_dim action dimensions, which n_actions then counts; any other name is a discrete one's, as before
+        self.continuous = isinstance(self.env, str) and self.env in CONT_ENVS
+        if self.continuous:
+            self.env_info = cont_env_info(self.env)
+            self.env_info["n_actions"] = self.env_info["act_dim"]
+        else:
+            self.env_info = env_info(self.env)
+        count = (lambda k: f"act_dim {k}") if self.continuous else (lambda k: f"{k} actions")
         # A config that names its environment must fit it.  Without the key the agent may be one that only
         # updates from given paths, of any shape; learn() then refuses the default environment if it does not fit.
         self.env_mismatch = None
         if (int(obs_dim), int(n_actions)) != (self.env_info["obs_dim"], self.env_info["n_actions"]):
             self.env_mismatch = (f"{self.env} has obs_dim {self.env_info['obs_dim']} and "
-                                 f"{self.env_info['n_actions']} actions; the agent was given obs_dim {obs_dim} "
-                                 f"and {n_actions} actions")
+                                 f"{count(self.env_info['n_actions'])}; the agent was given obs_dim {obs_dim} "
+                                 f"and {count(n_actions)}")
             if "env" in self.config:
                 raise ValueError("config['env']: " + self.env_mismatch)
-        self.engine = Engine(obs_dim, hidden, n_actions, max_rows, device)
-        self.session = Session(self.engine, reinit_policy=reinit_policy)
+        self.engine = Engine(obs_dim, hidden, n_actions, max_rows, device,
+                             dist="gaussian" if self.continuous else "categorical")
+        self.session = Session(self.engine, reinit_policy=reinit_policy,
+                               init_logstd=float(self.config.get("init_logstd", 0.0)) if self.continuous else None)
         self.gf = GetFlat(self.session)                          # trpo_inksci.py:71
         self.sff = SetFromFlat(self.session)                     # :72
         self.pg = flatgrad(SurrogateLoss(self.engine))           # :54
         self.fvp = flatgrad(KLFirstFixedGVP(self.engine))        # :56-70 (flatgrad(gvp))
-        self.sff(xavier_theta(obs_dim, hidden, n_actions, self.session.init_rng) if theta is None else theta)
+        self.sff(self.session.draw_theta() if theta is None else theta)
         self.train = True                                        # :28
         self.end_count = 0                                       # :29
         self.vf = VF(self.session, max_rows=max_rows, device=device)   # :73
@@ -197,8 +255,13 @@ class TRPOAgent:
 
     def feed(self, paths_or_batch, n_global: Optional[int] = None):
         """The feed dict of trpo_inksci.py:119-122 (+ rewards for :102-117)."""
-        b = paths_to_batch(paths_or_batch) if isinstance(paths_or_batch, list) else paths_or_batch
-        self.engine.set_batch(b["state"], b["action"], b.get("advant"), b["action_dist"], n_global)
+        if self.continuous:
+            b = gaussian_paths_to_batch(paths_or_batch) if isinstance(paths_or_batch, list) else paths_or_batch
+            self.engine.set_batch_gaussian(b["state"], b["action"], b.get("advant"), b["action_mean"], b["logstd"],
+                                           n_global)
+        else:
+            b = paths_to_batch(paths_or_batch) if isinstance(paths_or_batch, list) else paths_or_batch
+            self.engine.set_batch(b["state"], b["action"], b.get("advant"), b["action_dist"], n_global)
         if "rewards" in b:
             self.engine.set_rewards(b["rewards"], b["starts"], b.get("baseline"))
             if b.get("tail_values") is not None:
@@ -248,6 +311,8 @@ class TRPOAgent:
         (the reference calls exit(-1)).  max_iterations bounds the loop (None: as the reference).
         draws(i) -> (reset_uniforms, action_uniforms, max_episodes_per_env) injects the random draws
         of iteration i's rollout (env.reset and cat_sample; tests), else a Philox stream per iteration.
+        On a continuous-action environment the rollout calls are the Gaussian ones: draws(i)'s second entry is
+        then the standard normals of the act, and the record's "rollout" / "ends" are the Gaussian fetch dicts.
         record=True also returns each iteration's rollout arrays, baselines, returns and
         standardised advantages, and how its paths ended ("ends", Engine.rollout_fetch_ends) with the
         feed's "tail_values" (zeros unless config["bootstrap_truncated"] set some) (host copies; parity tests).
@@ -275,13 +340,18 @@ class TRPOAgent:
             inj = {}
             if draws is not None:
                 ru, au, me = draws(i)
-                inj = {"reset_uniforms": ru, "action_uniforms": au, "max_episodes_per_env": me}
-            n, n_paths = eng.rollout(self.env, n_envs=n_envs, n_timesteps=n_timesteps,
-                                     max_pathlength=cfg["max_steps"],
-                                     seed=rollout_seed(seed, i, self.rank),
-                                     train=self.train, **inj)                            # :96-100
+                inj = {"reset_uniforms": ru, "action_normals" if self.continuous else "action_uniforms": au,
+                       "max_episodes_per_env": me}
+            roll = eng.rollout_gaussian if self.continuous else eng.rollout
+            n, n_paths = roll(self.env, n_envs=n_envs, n_timesteps=n_timesteps,
+                              max_pathlength=cfg["max_steps"],
+                              seed=rollout_seed(seed, i, self.rank),
+                              train=self.train, **inj)                                   # :96-100
             n_global = int(self._host_sum(n)[0])
-            eng.rollout_to_batch(n_global=n_global)                                      # :108-122
+            if self.continuous:
+                eng.rollout_gaussian_to_batch(n_global=n_global)
+            else:
+                eng.rollout_to_batch(n_global=n_global)                                  # :108-122
             have_base = self.vf.predict_engine(eng)                                      # :103
             if record:
                 rb = self.vf.net.predict(np.empty(n, np.float64)) if have_base else np.zeros(n)
@@ -302,8 +372,10 @@ class TRPOAgent:
             rec = {"iteration": i, "steps": n, "paths": n_paths, "train": self.train,
                    "reward_mean": float(reward_mean), "end_count": self.end_count}
             if record:
-                rec.update({"rollout": eng.rollout_fetch(), "baseline": rb, "returns": r_ret, "advantages": r_adv,
-                            "ends": eng.rollout_fetch_ends(), "tail_values": r_tail})
+                fetch, fetch_ends = ((eng.rollout_gaussian_fetch, eng.rollout_gaussian_fetch_ends)
+                                     if self.continuous else (eng.rollout_fetch, eng.rollout_fetch_ends))
+                rec.update({"rollout": fetch(), "baseline": rb, "returns": r_ret, "advantages": r_adv,
+                            "ends": fetch_ends(), "tail_values": r_tail})
             if reward_mean > reward_target:                                              # :135-136
                 self.train = False
             rec["train"] = self.train                    # whether this iteration updates the policy

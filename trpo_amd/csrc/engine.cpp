@@ -332,8 +332,14 @@ struct trpo_engine {
     uint8_t* cat_truncated = nullptr;
     float *cat_obs32 = nullptr, *cat_dist = nullptr;
     int64_t *cat_len = nullptr, *cat_rows = nullptr;
+    // a Gaussian engine's rollout (trpo_rollout_gaussian): dist, end_dist and cat_dist hold means; the actions
+    // [rows][A] f32, the normals [rows][A] and the log-std vector [A] the rollout sampled with
+    float* actf = nullptr;
+    double* normals = nullptr;
+    float* logstd = nullptr;
   } roll;
   RolloutArgs roll_args{};
+  GaussRolloutArgs groll_args{};   // the last rollout of a Gaussian engine (roll_valid)
   int64_t roll_n = 0, roll_paths = 0, roll_maxcount = 0, roll_maxpaths = 0;
   bool roll_valid = false;
   bool feed_is_rollout = false;   // the feed is the one trpo_rollout_to_batch loaded (trpo_get_tail_view)
@@ -780,22 +786,26 @@ struct trpo_engine {
     a.end_row = roll.end_row;
     launch_rollout(a, stream);
     check_launch();
-    // row offsets [n_envs], then path offsets [n_envs]: one upload
-    std::vector<int64_t> counts(p.n_envs), eps(p.n_envs), offs((size_t)2 * p.n_envs);
+    roll_args = a;
+    rollout_offsets(p.n_envs);
+  }
+
+  // after a rollout kernel: row offsets [n_envs], then path offsets [n_envs] (one upload), and the totals
+  void rollout_offsets(int n_envs) {
+    std::vector<int64_t> counts(n_envs), eps(n_envs), offs((size_t)2 * n_envs);
     copy_out(counts.data(), roll.counts, counts.size() * sizeof(int64_t), TRPO_MEM_HOST);
     copy_out(eps.data(), roll.episodes, eps.size() * sizeof(int64_t), TRPO_MEM_HOST);
     int64_t tot = 0, mx = 0, ptot = 0, pmx = 0;
-    for (int i = 0; i < p.n_envs; ++i) {
+    for (int i = 0; i < n_envs; ++i) {
       offs[i] = tot;
       tot += counts[i];
       mx = std::max(mx, counts[i]);
-      offs[p.n_envs + i] = ptot;
+      offs[n_envs + i] = ptot;
       ptot += eps[i];
       pmx = std::max(pmx, eps[i]);
     }
     copy_in(roll.offsets, offs.data(), offs.size() * sizeof(int64_t), TRPO_MEM_HOST);
-    roll.path_offsets = roll.offsets + p.n_envs;
-    roll_args = a;
+    roll.path_offsets = roll.offsets + n_envs;
     roll_n = tot;
     roll_maxcount = mx;
     roll_paths = ptot;
@@ -806,6 +816,116 @@ struct trpo_engine {
   void rollout_compact(const RolloutOut& o) {
     REQUIRE(roll_valid, "no rollout to fetch");
     launch_rollout_compact(roll_args, roll.offsets, o, o.ends_only ? roll_maxpaths : roll_maxcount, stream);
+    check_launch();
+  }
+
+  // The same rollout of a continuous-action environment under this Gaussian engine's policy (rollout.hip).  The
+  // log-std vector is copied aside first: the rollout samples with the copy, and the feed built from it
+  // (trpo_rollout_gaussian_to_batch) takes it as the old log-std whatever theta has become since.
+  void rollout_gaussian(int cenv, const trpo_rollout_params& p) {
+    ContEnvDims ed{};
+    REQUIRE(cont_env_dims(cenv, &ed), "unknown continuous environment id " + std::to_string(cenv));
+    REQUIRE(p.n_envs >= 1 && p.n_envs <= (1 << 20), "n_envs out of range");
+    REQUIRE(p.n_timesteps >= 1 && p.max_pathlength >= 1 && p.time_limit >= 1, "bad rollout lengths");
+    REQUIRE(w[0] == ed.obs_dim && w[L] == ed.act_dim,
+            std::string(ed.name) + " needs obs_dim " + std::to_string(ed.obs_dim) + " and act_dim " +
+                std::to_string(ed.act_dim) + "; the engine has obs_dim " + std::to_string(w[0]) + " and act_dim " +
+                std::to_string(w[L]));
+    const int obs_dim = ed.obs_dim, A = ed.act_dim;
+    const int state_cap = ed.state_dim == ed.obs_dim ? 0 : ed.state_dim;
+    const int ep_max = std::min(p.max_pathlength, p.time_limit);
+    const int64_t budget = (p.n_timesteps + p.n_envs - 1) / p.n_envs;
+    const int64_t env_cap = budget + ep_max - 1;
+    const int64_t rows = env_cap * p.n_envs;
+    REQUIRE(rows <= (int64_t(1) << 34), "rollout too large");
+    const int64_t paths = budget * p.n_envs;
+    if (p.reset_uniforms) {
+      REQUIRE(p.max_episodes_per_env >= 1, "max_episodes_per_env required with reset_uniforms");
+      REQUIRE((int64_t)p.max_episodes_per_env >= budget, "max_episodes_per_env must be >= ceil(n_timesteps/n_envs)");
+    }
+    feed_is_rollout = false;
+    roll_valid = false;   // the regions are about to be overwritten
+    if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths || state_cap > roll.state_cap) {
+      for (void* ptr : roll.mem) HIPCHECK(hipFree(ptr));
+      roll = RollBufs{};
+      roll.rows = rows;
+      roll.envs = p.n_envs;
+      roll.paths = paths;
+      roll.end_truncated = ralloc<uint8_t>(paths);
+      roll.end_obs = ralloc<double>((size_t)paths * obs_dim);
+      roll.end_dist = ralloc<float>((size_t)paths * A);
+      roll.end_len = ralloc<int64_t>(paths);
+      roll.end_row = ralloc<int64_t>(paths);
+      roll.cat_truncated = ralloc<uint8_t>(paths);
+      roll.cat_obs32 = ralloc<float>((size_t)paths * obs_dim);
+      roll.cat_dist = ralloc<float>((size_t)paths * A);
+      roll.cat_len = ralloc<int64_t>(paths);
+      roll.cat_rows = ralloc<int64_t>(paths);
+      roll.obs = ralloc<double>((size_t)rows * obs_dim);
+      roll.state_cap = state_cap;
+      if (state_cap) roll.env_state = ralloc<double>((size_t)rows * state_cap);
+      roll.actf = ralloc<float>((size_t)rows * A);
+      roll.dist = ralloc<float>((size_t)rows * A);
+      roll.normals = ralloc<double>((size_t)rows * A);
+      roll.logstd = ralloc<float>(A);
+      roll.rewards = ralloc<double>(rows);
+      roll.starts = ralloc<uint8_t>(rows);
+      roll.counts = ralloc<int64_t>(p.n_envs);
+      roll.episodes = ralloc<int64_t>(p.n_envs);
+      roll.offsets = ralloc<int64_t>((size_t)2 * p.n_envs);
+    }
+    GaussRolloutArgs a{};
+    a.cenv = cenv;
+    a.state_dim = ed.state_dim;
+    a.ps = policy_shape();
+    a.theta = theta;
+    a.logstd = roll.logstd;
+    a.maxw = max_width();
+    a.n_envs = p.n_envs;
+    a.max_pathlength = p.max_pathlength;
+    a.time_limit = p.time_limit;
+    a.train = p.train;
+    a.budget = budget;
+    a.env_cap = env_cap;
+    a.max_episodes = p.max_episodes_per_env;
+    a.seed = p.seed;
+    // optional injected draws (tests): reset uniforms [n_envs][max_episodes][reset_draws], normals [n_envs][env_cap][A]
+    auto stage_u = [&](const double* src, int64_t count, double*& buf, int64_t& cap_n) -> const double* {
+      if (!src) return nullptr;
+      if (p.mem == TRPO_MEM_DEVICE) return src;
+      if (count > cap_n) {
+        buf = ralloc<double>(count);
+        cap_n = count;
+      }
+      copy_in(buf, src, (size_t)count * sizeof(double), TRPO_MEM_HOST);
+      return buf;
+    };
+    a.reset_u = stage_u(p.reset_uniforms, (int64_t)p.n_envs * std::max(1, p.max_episodes_per_env) * ed.reset_draws,
+                        roll.reset_u, roll.reset_u_n);
+    a.act_n = stage_u(p.action_uniforms, rows * A, roll.act_u, roll.act_u_n);
+    HIPCHECK(hipMemcpyAsync(roll.logstd, logstd_of(theta), (size_t)A * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    a.obs = roll.obs;
+    a.env_state = state_cap ? roll.env_state : nullptr;
+    a.actions = roll.actf;
+    a.means = roll.dist;
+    a.normals = roll.normals;
+    a.rewards = roll.rewards;
+    a.starts = roll.starts;
+    a.counts = roll.counts;
+    a.episodes = roll.episodes;
+    a.end_truncated = roll.end_truncated;
+    a.end_obs = roll.end_obs;
+    a.end_mean = roll.end_dist;
+    a.end_len = roll.end_len;
+    a.end_row = roll.end_row;
+    launch_rollout_gaussian(a, stream);
+    check_launch();
+    groll_args = a;
+    rollout_offsets(p.n_envs);
+  }
+
+  void rollout_gaussian_compact(const GaussRolloutOut& o) {
+    launch_rollout_gaussian_compact(groll_args, roll.offsets, o, o.ends_only ? roll_maxpaths : roll_maxcount, stream);
     check_launch();
   }
 
@@ -2884,6 +3004,114 @@ int trpo_act_gaussian(trpo_engine* e, const float* states, int64_t n, const doub
                         e->stream);
     check_launch();
     st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+// ---- the Gaussian engine's rollouts of the continuous-action environments ----------------------------------
+int trpo_rollout_gaussian(trpo_engine* e, int cenv, const trpo_rollout_params* p, int64_t* n_steps_out,
+                          int64_t* n_paths_out) {
+  return guarded([&] {
+    REQUIRE(e && p, "NULL argument");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian");
+    REQUIRE(e->w[e->L] <= 64, "rollout_gaussian: act_dim must be <= 64 (one wave per environment)");
+    e->use();
+    e->rollout_gaussian(cenv, *p);
+    if (n_steps_out) *n_steps_out = e->roll_n;
+    if (n_paths_out) *n_paths_out = e->roll_paths;
+  });
+}
+
+int trpo_rollout_gaussian_fetch(trpo_engine* e, double* obs, float* obs32, float* actions, float* means,
+                                float* logstd, double* rewards, uint8_t* episode_starts, double* normals,
+                                double* env_states, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian_fetch");
+    if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
+    e->use();
+    const int64_t N = e->roll_n;
+    const int obs_dim = e->w[0], A = e->w[e->L];
+    GaussRolloutOut o{};
+    Staging st(mem, e->stream);
+    o.obs64 = st.out(obs, (size_t)N * obs_dim);
+    o.X = st.out(obs32, (size_t)N * obs_dim);
+    o.ldx = obs_dim;
+    o.actions = st.out(actions, (size_t)N * A);
+    o.ld_act = A;
+    o.means = st.out(means, (size_t)N * A);
+    o.ld_mean = A;
+    o.normals = st.out(normals, (size_t)N * A);
+    o.rewards = st.out(rewards, (size_t)N);
+    o.starts = st.out(episode_starts, (size_t)N);
+    o.env_state = st.out(env_states, (size_t)N * e->groll_args.state_dim);
+    e->rollout_gaussian_compact(o);
+    st.fetch();
+    if (logstd) e->copy_out(logstd, e->roll.logstd, (size_t)A * sizeof(float), mem);
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int trpo_rollout_gaussian_fetch_ends(trpo_engine* e, uint8_t* truncated, double* final_obs, float* final_means,
+                                     int64_t* lengths, int64_t* end_rows, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian_fetch_ends");
+    if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
+    e->use();
+    const int64_t P = e->roll_paths;
+    const int obs_dim = e->w[0], A = e->w[e->L];
+    GaussRolloutOut o{};
+    Staging st(mem, e->stream);
+    o.ends_only = 1;
+    o.path_offsets = e->roll.path_offsets;
+    o.end_truncated = st.out(truncated, (size_t)P);
+    o.end_obs64 = st.out(final_obs, (size_t)P * obs_dim);
+    o.end_mean = st.out(final_means, (size_t)P * A);
+    o.end_len = st.out(lengths, (size_t)P);
+    o.end_rows = st.out(end_rows, (size_t)P);
+    e->rollout_gaussian_compact(o);
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int trpo_rollout_gaussian_to_batch(trpo_engine* e, int64_t n_global) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian_to_batch");
+    if (!e->roll_valid) throw std::runtime_error("no rollout to load");
+    const int64_t N = e->roll_n;
+    REQUIRE(N <= e->cap, "rollout has more steps than max_rows");
+    REQUIRE(n_global >= N, "n_global must be >= the rollout's steps");
+    e->use();
+    const int A = e->w[e->L];
+    GaussRolloutOut o{};
+    o.X = e->X;
+    o.ldx = e->wp[0];
+    o.actions = e->actf;
+    o.ld_act = e->wp[e->L];
+    o.means = e->old;
+    o.ld_mean = e->wp[e->L];
+    o.rewards = e->rewards;
+    o.starts = e->starts;
+    // the paths' end records, for trpo_get_tail_view
+    o.path_offsets = e->roll.path_offsets;
+    o.end_truncated = e->roll.cat_truncated;
+    o.end_obs32 = e->roll.cat_obs32;
+    o.end_mean = e->roll.cat_dist;
+    o.end_len = e->roll.cat_len;
+    o.end_rows = e->roll.cat_rows;
+    e->rollout_gaussian_compact(o);
+    HIPCHECK(hipMemcpyAsync(e->logstd0, e->roll.logstd, (size_t)A * sizeof(float), hipMemcpyDeviceToDevice,
+                            e->stream));
+    e->n = N;
+    e->n_global = n_global;
+    e->update_x_amax();
+    e->feed_loaded();
+    e->feed_is_rollout = true;
+    e->have_rewards = true;
+    e->have_baseline = false;
     HIPCHECK(hipStreamSynchronize(e->stream));
   });
 }

@@ -854,6 +854,71 @@ void launch_cartpole_step(const double* state, const int64_t* action, int64_t n,
 // state [n][state_dim] -> state_out, obs_out [n][obs_dim], reward, done (termination); outputs may be NULL
 void launch_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out,
                      double* obs_out, double* reward, uint8_t* done, hipStream_t s);
+
+// The continuous-action environments (TRPO_CENV_*) under the diagonal-Gaussian policy: the same per-wave rollout
+// with the Gaussian act (launch_act_gaussian's arithmetic) in place of softmax + cat_sample.
+struct ContEnvDims {        // one continuous-action environment, from its trait in rollout.hip
+  int obs_dim, state_dim, act_dim, reset_draws, time_limit;
+  const char* name;
+};
+bool cont_env_dims(int cenv, ContEnvDims* out);   // host-only; false for an unknown id
+struct GaussRolloutArgs {
+  int cenv;                 // TRPO_CENV_*; ps must have its obs_dim and act_dim
+  int state_dim;            // the environment's
+  PolicyShape ps;
+  const float* theta;
+  const float* logstd;      // [A] the log-stds the rollout samples with (the engine's snapshot)
+  int maxw;
+  int n_envs, max_pathlength, time_limit, train;
+  int64_t budget, env_cap;  // as RolloutArgs
+  int max_episodes;
+  uint64_t seed;
+  const double* reset_u;    // optional [n_envs][max_episodes][reset_draws] uniforms for env.reset
+  const double* act_n;      // optional [n_envs][env_cap][A] standard normals for the act
+  // per-environment regions (row = env * env_cap + i)
+  double* obs;              // [.][obs_dim]
+  double* env_state;        // [.][state_dim]; NULL where the observation is the state
+  float* actions;           // [.][A]
+  float* means;             // [.][A]
+  double* normals;          // [.][A] the normal of every action component (0 when train = 0)
+  double* rewards;
+  uint8_t* starts;
+  int64_t* counts;          // [n_envs]
+  int64_t* episodes;        // [n_envs]
+  // per-environment path regions (path = env * budget + episode)
+  uint8_t* end_truncated;
+  double* end_obs;          // [.][obs_dim]
+  float* end_mean;          // [.][A] the policy's mean at s_T of a cut-off path, zeros otherwise
+  int64_t* end_len;
+  int64_t* end_row;
+};
+struct GaussRolloutOut {    // concatenated outputs; any pointer may be NULL
+  double* obs64;            // [N][obs_dim]
+  double* env_state;        // [N][state_dim]
+  float* X;                 // [N][ldx]
+  int ldx;
+  float* actions;           // [N][ld_act]
+  int ld_act;
+  float* means;             // [N][ld_mean]
+  int ld_mean;
+  double* normals;          // [N][A]
+  double* rewards;
+  uint8_t* starts;
+  const int64_t* path_offsets;   // as RolloutOut: the end records are written when given
+  int ends_only;
+  uint8_t* end_truncated;
+  double* end_obs64;        // [n_paths][obs_dim]
+  float* end_obs32;
+  float* end_mean;          // [n_paths][A]
+  int64_t* end_len;
+  int64_t* end_rows;
+};
+void launch_rollout_gaussian(const GaussRolloutArgs& a, hipStream_t s);
+void launch_rollout_gaussian_compact(const GaussRolloutArgs& a, const int64_t* offsets, const GaussRolloutOut& o,
+                                     int64_t max_count, hipStream_t s);
+// state [n][state_dim], action [n][act_dim] f32 -> state_out, obs_out [n][obs_dim], reward, done; outputs may be NULL
+void launch_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
+                          double* obs_out, double* reward, uint8_t* done, hipStream_t s);
 }  // namespace trpo
 
 namespace trpo {

@@ -17,6 +17,10 @@
 //     restated the same way (include/trpo_engine.h spells out their equations).  The rollout is one
 //     kernel over an environment trait (reset, step, observe and the dimensions), so that a task whose
 //     state is not its observation (Acrobot) or whose reward is not constant costs no second kernel.
+//   * Pendulum-v1 and MountainCarContinuous-v0 under the diagonal-Gaussian policy: the same rollout over a
+//     continuous-action trait, which steps with the float32 action components, sampled as act_gaussian does
+//     (gauss_act) from Box-Muller normals off the same Philox stream; it records action, mean and normal per
+//     component, and samples with the copy of the log-std vector the engine took when the rollout began.
 //
 // One wave simulates one environment for its whole share of the rollout: the
 // policy forward is wave-parallel over output units (activations in a per-wave
@@ -75,6 +79,16 @@ __device__ __forceinline__ double uniform53(uint64_t seed, uint32_t env, uint32_
   philox(c, seed);
   const uint32_t a = c[0] >> 5, b = c[1] >> 6;
   return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+}
+
+// standard normal by Box-Muller off one Philox call: u1 from (c0, c1), u2 from (c2, c3), both by uniform53's recipe;
+// xi = sqrt(-2 log(1 - u1)) cos(2 pi u2)  (1 - u1 is in (0, 1], so the log is finite)
+__device__ __forceinline__ double normal53(uint64_t seed, uint32_t env, uint32_t stream, uint64_t draw) {
+  uint32_t c[4] = {env, stream, (uint32_t)draw, (uint32_t)(draw >> 32)};
+  philox(c, seed);
+  const double u1 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6)) / 9007199254740992.0;
+  const double u2 = ((double)(c[2] >> 5) * 67108864.0 + (double)(c[3] >> 6)) / 9007199254740992.0;
+  return sqrt(-2.0 * log(1.0 - u1)) * cos(2 * 3.141592653589793 * u2);
 }
 
 // ---- CartPole-v0 (gym classic_control/cartpole.py), float64 ------------------------------------
@@ -227,6 +241,77 @@ bool with_env(int env, F&& f) {
   }
 }
 
+// ---- the continuous-action environments (TRPO_CENV_*; include/trpo_engine.h spells out their equations) ----
+// A trait of this kind steps with the kActDim float32 action components the policy produced, widened to float64.
+
+// Pendulum-v1 (gym classic_control/pendulum.py), float64
+struct PendulumV1 {
+  static constexpr int kState = 2, kObs = 3, kActDim = 1, kResetDraws = 2, kTimeLimit = 200;
+  static constexpr bool kObsIsState = false;
+  static constexpr const char* kName = "Pendulum-v1";
+  static constexpr double kPi = 3.141592653589793;
+  static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
+    s[0] = -kPi + (kPi - -kPi) * u[0];
+    s[1] = -1.0 + (1.0 - -1.0) * u[1];
+  }
+  static __device__ __forceinline__ bool step(double (&s)[kState], const float (&act)[kActDim], double& reward) {
+    const double th = s[0], thd = s[1];
+    const double u = clampd((double)act[0], -2.0, 2.0);
+    const double y = th + kPi;
+    double m = fmod(y, 2 * kPi);
+    if (m < 0.0) m = m + 2 * kPi;
+    const double an = m - kPi;
+    const double cost = an * an + 0.1 * (thd * thd) + 0.001 * (u * u);
+    double thd1 = thd + (3 * 10.0 / (2 * 1.0) * sin(th) + 3.0 / (1.0 * (1.0 * 1.0)) * u) * 0.05;
+    thd1 = clampd(thd1, -8.0, 8.0);
+    s[0] = th + thd1 * 0.05;
+    s[1] = thd1;
+    reward = -cost;
+    return false;
+  }
+  // (cos th, sin th, thd)
+  static __device__ __forceinline__ double observe(const double (&s)[kState], int i) {
+    return i == 0 ? cos(s[0]) : (i == 1 ? sin(s[0]) : s[1]);
+  }
+};
+
+// MountainCarContinuous-v0 (gym classic_control/continuous_mountain_car.py), float64
+struct MountainCarContinuousV0 {
+  static constexpr int kState = 2, kObs = 2, kActDim = 1, kResetDraws = 1, kTimeLimit = 999;
+  static constexpr bool kObsIsState = true;
+  static constexpr const char* kName = "MountainCarContinuous-v0";
+  static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
+    s[0] = -0.6 + (-0.4 - -0.6) * u[0];
+    s[1] = 0.0;
+  }
+  static __device__ __forceinline__ bool step(double (&s)[kState], const float (&act)[kActDim], double& reward) {
+    const double a = (double)act[0];
+    double p = s[0], v = s[1];
+    const double f = clampd(a, -1.0, 1.0);
+    v = v + f * 0.0015 + cos(3.0 * p) * (-0.0025);
+    v = clampd(v, -0.07, 0.07);
+    p = p + v;
+    p = clampd(p, -1.2, 0.6);
+    if (p == -1.2 && v < 0.0) v = 0.0;
+    s[0] = p;
+    s[1] = v;
+    const bool done = p >= 0.45 && v >= 0.0;
+    reward = (done ? 100.0 : 0.0) - (a * a) * 0.1;   // the unclamped action, as gym's
+    return done;
+  }
+  static __device__ __forceinline__ double observe(const double (&s)[kState], int i) { return s[i]; }
+};
+
+// continuous env id (TRPO_CENV_*) -> trait; false for an unknown id
+template <class F>
+bool with_cenv(int cenv, F&& f) {
+  switch (cenv) {
+    case 0: f(PendulumV1{}); return true;
+    case 1: f(MountainCarContinuousV0{}); return true;
+    default: return false;
+  }
+}
+
 // ---- wave-level policy forward ---------------------------------------------------------------
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -303,6 +388,14 @@ __device__ __forceinline__ int wave_choose(float p, int A, double r, int train, 
   }
   (void)lane;
   return out;
+}
+
+// the diagonal-Gaussian policy's sample of one action component (include/trpo_engine.h, TRPO_DIST_GAUSSIAN):
+// a = float32(mu + exp(s) * xi), the product and the sum in float64.  act_gaussian_kernel and the Gaussian rollout
+// both sample through it.
+__device__ __forceinline__ float gauss_act(float mu, float logstd, double xi) {
+  const double noise = exp((double)logstd) * xi;
+  return (float)((double)mu + noise);
 }
 
 constexpr int kRollWaves = 4;
@@ -477,14 +570,140 @@ __global__ void __launch_bounds__(kRollWaves * 64) act_gaussian_kernel(const Pol
   if (lane < A) {
     const float m = mu[lane];
     if (means) means[row * A + lane] = m;
-    if (actions) {
-      float a = m;
-      if (train) {
-        const double noise = exp((double)logstd[lane]) * normals[row * A + lane];
-        a = (float)((double)m + noise);
+    if (actions) actions[row * A + lane] = train ? gauss_act(m, logstd[lane], normals[row * A + lane]) : m;
+  }
+}
+
+// The rollout under the diagonal-Gaussian policy: rollout_kernel with the mean forward and gauss_act in place of
+// softmax + cat_sample, over a continuous-action environment trait.  The normal of component d at an environment's
+// step k (counted over all its episodes, whether or not train) is Philox (seed, env, stream 0, k * A + d).
+template <class Env>
+__global__ void __launch_bounds__(kRollWaves * 64) rollout_gaussian_kernel(const GaussRolloutArgs a) {
+  extern __shared__ float lds[];
+  constexpr int kS = Env::kState, obs_dim = Env::kObs, A = Env::kActDim;   // the engine checked ps against them
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int env = blockIdx.x * kRollWaves + wv;
+  if (env >= a.n_envs) return;
+  float* buf0 = lds + (size_t)wv * 2 * a.maxw;
+  float* buf1 = buf0 + a.maxw;
+  const int64_t base = (int64_t)env * a.env_cap;
+  int64_t count = 0;
+  int episode = 0;
+  while (count < a.budget) {
+    double u[Env::kResetDraws];
+#pragma unroll
+    for (int i = 0; i < Env::kResetDraws; ++i)
+      u[i] = a.reset_u ? a.reset_u[((int64_t)env * a.max_episodes + episode) * Env::kResetDraws + i]
+                       : uniform53(a.seed, (uint32_t)env, 1u, (uint64_t)episode * Env::kResetDraws + i);
+    double s[kS];
+    Env::reset(s, u);
+    ++episode;
+    bool done = false;
+    int len = 0;
+    for (int t = 0; t < a.max_pathlength; ++t) {
+      const int64_t row = base + count;
+      if (lane < obs_dim) {
+        const double ob = Env::observe(s, lane);
+        buf0[lane] = (float)ob;
+        a.obs[row * obs_dim + lane] = ob;
       }
-      actions[row * A + lane] = a;
+      if constexpr (!Env::kObsIsState) {
+        if (lane < kS) a.env_state[row * kS + lane] = s[lane];
+      }
+      wave_sync();
+      const float* mu = wave_layers(a.ps, a.theta, buf0, buf1, lane);
+      // every lane forms the whole action, as it holds the whole state; lane d records component d
+      float act[A];
+#pragma unroll
+      for (int d = 0; d < A; ++d) {
+        const float m = mu[d];
+        double xi = 0.0;
+        if (a.train)
+          xi = a.act_n ? a.act_n[row * A + d] : normal53(a.seed, (uint32_t)env, 0u, (uint64_t)count * A + d);
+        act[d] = a.train ? gauss_act(m, a.logstd[d], xi) : m;
+        if (lane == d) {
+          a.actions[row * A + d] = act[d];
+          a.means[row * A + d] = m;
+          a.normals[row * A + d] = xi;
+        }
+      }
+      double reward;
+      done = Env::step(s, act, reward);
+      if (lane == 0) {
+        a.rewards[row] = reward;
+        a.starts[row] = t == 0 ? 1 : 0;
+      }
+      ++count;
+      len = t + 1;
+      if (done || t + 1 >= a.time_limit) break;
+      wave_sync();
     }
+    wave_sync();
+    // how the path ended, as rollout_kernel records it; a cut-off path records the policy's mean at s_T
+    const int64_t path = (int64_t)env * a.budget + (episode - 1);
+    const bool truncated = !done;
+    const double obT = lane < obs_dim ? Env::observe(s, lane) : 0.0;
+    float muT = 0.0f;
+    if (truncated) {
+      if (lane < obs_dim) buf0[lane] = (float)obT;
+      wave_sync();
+      const float* mu = wave_layers(a.ps, a.theta, buf0, buf1, lane);
+      if (lane < A) muT = mu[lane];
+      wave_sync();
+    }
+    if (lane < obs_dim) a.end_obs[path * obs_dim + lane] = obT;
+    if (lane < A) a.end_mean[path * A + lane] = muT;
+    if (lane == 0) {
+      a.end_truncated[path] = truncated ? 1 : 0;
+      a.end_len[path] = len;
+      a.end_row[path] = count - 1;
+    }
+  }
+  if (lane == 0) {
+    a.counts[env] = count;
+    a.episodes[env] = episode;
+  }
+}
+
+// concatenate the per-environment regions of a Gaussian rollout in environment order
+__global__ void __launch_bounds__(256) rollout_gaussian_compact_kernel(const GaussRolloutArgs a,
+                                                                       const int64_t* offsets, GaussRolloutOut o) {
+  const int obs_dim = a.ps.w[0], A = a.ps.w[a.ps.L];
+  const int env = blockIdx.y;
+  const int64_t cnt = o.ends_only ? 0 : a.counts[env], dst0 = offsets[env], src0 = (int64_t)env * a.env_cap;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = src0 + i, d = dst0 + i;
+    for (int c = 0; c < obs_dim; ++c) {
+      const double v = a.obs[s * obs_dim + c];
+      if (o.obs64) o.obs64[d * obs_dim + c] = v;
+      if (o.X) o.X[d * o.ldx + c] = (float)v;
+    }
+    for (int c = 0; c < A; ++c) {
+      if (o.actions) o.actions[d * o.ld_act + c] = a.actions[s * A + c];
+      if (o.means) o.means[d * o.ld_mean + c] = a.means[s * A + c];
+      if (o.normals) o.normals[d * A + c] = a.normals[s * A + c];
+    }
+    if (o.rewards) o.rewards[d] = a.rewards[s];
+    if (o.starts) o.starts[d] = a.starts[s];
+    if (o.env_state) {   // an environment whose observation is its state recorded it once, as obs
+      const double* st = a.env_state ? a.env_state : a.obs;
+      for (int c = 0; c < a.state_dim; ++c) o.env_state[d * a.state_dim + c] = st[s * a.state_dim + c];
+    }
+  }
+  if (!o.path_offsets) return;
+  const int64_t np = a.episodes[env], pdst0 = o.path_offsets[env], psrc0 = (int64_t)env * a.budget;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = psrc0 + i, d = pdst0 + i;
+    for (int c = 0; c < obs_dim; ++c) {
+      const double v = a.end_obs[s * obs_dim + c];
+      if (o.end_obs64) o.end_obs64[d * obs_dim + c] = v;
+      if (o.end_obs32) o.end_obs32[d * obs_dim + c] = (float)v;
+    }
+    if (o.end_mean)
+      for (int c = 0; c < A; ++c) o.end_mean[d * A + c] = a.end_mean[s * A + c];
+    if (o.end_truncated) o.end_truncated[d] = a.end_truncated[s];
+    if (o.end_len) o.end_len[d] = a.end_len[s];
+    if (o.end_rows) o.end_rows[d] = dst0 + a.end_row[s];
   }
 }
 
@@ -528,6 +747,34 @@ __global__ void __launch_bounds__(256) env_step_kernel(const double* state, cons
     for (int j = 0; j < kS; ++j) s[j] = state[kS * i + j];
     double rw;
     const bool d = Env::step(s, (int)action[i], rw);
+    if (state_out) {
+#pragma unroll
+      for (int j = 0; j < kS; ++j) state_out[kS * i + j] = s[j];
+    }
+    if (obs_out) {
+#pragma unroll
+      for (int j = 0; j < kO; ++j) obs_out[kO * i + j] = Env::observe(s, j);
+    }
+    if (reward) reward[i] = rw;
+    if (done) done[i] = d ? 1 : 0;
+  }
+}
+
+// ... and of a continuous-action environment: action [n][kActDim] f32
+template <class Env>
+__global__ void __launch_bounds__(256) cont_env_step_kernel(const double* state, const float* action, int64_t n,
+                                                            double* state_out, double* obs_out, double* reward,
+                                                            uint8_t* done) {
+  constexpr int kS = Env::kState, kO = Env::kObs, kA = Env::kActDim;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    double s[kS];
+#pragma unroll
+    for (int j = 0; j < kS; ++j) s[j] = state[kS * i + j];
+    float act[kA];
+#pragma unroll
+    for (int j = 0; j < kA; ++j) act[j] = action[kA * i + j];
+    double rw;
+    const bool d = Env::step(s, act, rw);
     if (state_out) {
 #pragma unroll
       for (int j = 0; j < kS; ++j) state_out[kS * i + j] = s[j];
@@ -607,6 +854,38 @@ void launch_env_step(int env, const double* state, const int64_t* action, int64_
                        n, state_out, obs_out, reward, done);
   });
   if (!known) throw std::invalid_argument("launch_env_step: unknown environment id");
+}
+
+bool cont_env_dims(int cenv, ContEnvDims* out) {
+  return with_cenv(cenv, [&](auto e) {
+    using Env = decltype(e);
+    *out = ContEnvDims{Env::kObs, Env::kState, Env::kActDim, Env::kResetDraws, Env::kTimeLimit, Env::kName};
+  });
+}
+
+void launch_rollout_gaussian(const GaussRolloutArgs& a, hipStream_t s) {
+  const unsigned blocks = (unsigned)((a.n_envs + kRollWaves - 1) / kRollWaves);
+  const bool known = with_cenv(a.cenv, [&](auto e) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rollout_gaussian_kernel<decltype(e)>), dim3(blocks), dim3(kRollWaves * 64),
+                       rollout_lds_bytes(a.maxw), s, a);
+  });
+  if (!known) throw std::invalid_argument("launch_rollout_gaussian: unknown continuous environment id");
+}
+
+void launch_rollout_gaussian_compact(const GaussRolloutArgs& a, const int64_t* offsets, const GaussRolloutOut& o,
+                                     int64_t max_count, hipStream_t s) {
+  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_count + 255) / 256, 64));
+  hipLaunchKernelGGL(rollout_gaussian_compact_kernel, dim3(bx, a.n_envs), dim3(256), 0, s, a, offsets, o);
+}
+
+void launch_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
+                          double* obs_out, double* reward, uint8_t* done, hipStream_t s) {
+  const bool known = with_cenv(cenv, [&](auto e) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(cont_env_step_kernel<decltype(e)>), dim3(grid1(n)), dim3(256), 0, s, state,
+                       action, n, state_out, obs_out, reward, done);
+  });
+  if (!known) throw std::invalid_argument("launch_cont_env_step: unknown continuous environment id");
 }
 
 }  // namespace trpo

@@ -82,6 +82,51 @@ int trpo_env_step(int env, const double* state, const int64_t* action, int64_t n
   });
 }
 
+int trpo_cont_env_info(int cenv, trpo_cont_env_info_t* out) {
+  return guarded([&] {
+    REQUIRE(out, "NULL argument");
+    ContEnvDims d{};
+    REQUIRE(cont_env_dims(cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
+    std::memset(out, 0, sizeof *out);
+    out->obs_dim = d.obs_dim;
+    out->state_dim = d.state_dim;
+    out->act_dim = d.act_dim;
+    out->reset_draws = d.reset_draws;
+    out->time_limit = d.time_limit;
+    std::strncpy(out->name, d.name, sizeof out->name - 1);
+  });
+}
+
+int trpo_default_rollout_params_cont(int cenv, trpo_rollout_params* p) {
+  return guarded([&] {
+    REQUIRE(p, "NULL argument");
+    ContEnvDims d{};
+    REQUIRE(cont_env_dims(cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
+    trpo_default_rollout_params(p);
+    p->time_limit = d.time_limit;
+  });
+}
+
+int trpo_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
+                       double* obs_out, double* reward, uint8_t* done, int mem) {
+  return guarded([&] {
+    ContEnvDims d{};
+    REQUIRE(cont_env_dims(cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
+    REQUIRE(state && action && n >= 0, "bad argument");
+    if (n == 0) return;
+    Staging st(mem, nullptr);
+    const double* ds = st.in(state, (size_t)n * d.state_dim);
+    const float* da = st.in(action, (size_t)n * d.act_dim);
+    double* dso = st.out(state_out, (size_t)n * d.state_dim);
+    double* dob = st.out(obs_out, (size_t)n * d.obs_dim);
+    double* dr = st.out(reward, (size_t)n);
+    launch_cont_env_step(cenv, ds, da, n, dso, dob, dr, st.out(done, (size_t)n), nullptr);
+    check_launch();
+    st.fetch();
+    HIPCHECK(hipDeviceSynchronize());
+  });
+}
+
 int trpo_device_count(int* out) {
   return guarded([&] {
     REQUIRE(out, "NULL argument");

@@ -16,7 +16,8 @@ import numpy as np
 from . import _lib
 from ._lib import MEM_DEVICE, MEM_HOST, check, lib
 
-__all__ = ["Engine", "UpdateParams", "ENVS", "env_info", "env_step_device"]
+__all__ = ["Engine", "UpdateParams", "ENVS", "env_info", "env_step_device", "CONT_ENVS", "cont_env_info",
+           "cont_env_step_device"]
 
 _ADV_KINDS = {"returns": _lib.ADV_RETURNS, "gae": _lib.ADV_GAE}
 _DISTS = {"categorical": _lib.DIST_CATEGORICAL, "gaussian": _lib.DIST_GAUSSIAN}
@@ -40,6 +41,28 @@ def env_info(env) -> dict:
     info = _lib.EnvInfo()
     check(lib.trpo_env_info(_env_id(env), ctypes.byref(info)), "trpo_env_info")
     return {"obs_dim": info.obs_dim, "state_dim": info.state_dim, "n_actions": info.n_actions,
+            "reset_draws": info.reset_draws, "time_limit": info.time_limit, "name": info.name.decode()}
+
+
+# the continuous-action environments a Gaussian engine rolls out: name -> TRPO_CENV_* id
+CONT_ENVS = {"Pendulum-v1": _lib.CENV_PENDULUM_V1,
+             "MountainCarContinuous-v0": _lib.CENV_MOUNTAINCAR_CONTINUOUS_V0}
+
+
+def _cont_env_id(env) -> int:
+    if isinstance(env, str):
+        if env not in CONT_ENVS:
+            raise ValueError(f"unknown continuous environment {env!r}; built in: {sorted(CONT_ENVS)}")
+        return CONT_ENVS[env]
+    return int(env)
+
+
+def cont_env_info(env) -> dict:
+    """The table of a continuous-action environment (a name of CONT_ENVS or a TRPO_CENV_* id): obs_dim, state_dim,
+    act_dim, reset_draws, time_limit, name.  Host-only: needs no GPU."""
+    info = _lib.ContEnvInfo()
+    check(lib.trpo_cont_env_info(_cont_env_id(env), ctypes.byref(info)), "trpo_cont_env_info")
+    return {"obs_dim": info.obs_dim, "state_dim": info.state_dim, "act_dim": info.act_dim,
             "reset_draws": info.reset_draws, "time_limit": info.time_limit, "name": info.name.decode()}
 
 
@@ -121,6 +144,7 @@ class Engine:
             check(lib.trpo_create_dist(ctypes.byref(handle), _DISTS[dist], self.obs_dim, h, len(self.hidden),
                                        self.n_actions, self.max_rows, self.device), "trpo_create_dist")
         self._h = handle
+        self._gaussian = dist == "gaussian"
         self.num_params = int(lib.trpo_num_params(self._h))
         self.n = 0
         self.n_global = 0
@@ -525,6 +549,12 @@ class Engine:
         """Rewards and path starts of the last rollout (host; for the print-out statistics)."""
         N = self.rollout_steps
         rew, st = np.empty(N), np.empty(N, np.uint8)
+        if self._gaussian:
+            check(lib.trpo_rollout_gaussian_fetch(self._h, None, None, None, None, None,
+                                                  rew.ctypes.data_as(ctypes.c_void_p),
+                                                  st.ctypes.data_as(ctypes.c_void_p), None, None, MEM_HOST),
+                  "trpo_rollout_gaussian_fetch")
+            return {"rewards": rew, "starts": st}
         check(lib.trpo_rollout_fetch(self._h, None, None, None, None, rew.ctypes.data_as(ctypes.c_void_p),
                                      st.ctypes.data_as(ctypes.c_void_p), None, MEM_HOST), "trpo_rollout_fetch")
         return {"rewards": rew, "starts": st}
@@ -577,6 +607,89 @@ class Engine:
         N = self.rollout_steps
         check(lib.trpo_rollout_to_batch(self._h, N if n_global is None else int(n_global)), "trpo_rollout_to_batch")
         self.n, self.n_global = N, (N if n_global is None else int(n_global))
+        self._tail_ptr = None
+
+    # ------------------------------------------------------------------ continuous-action rollouts (Gaussian engine)
+    def rollout_gaussian(self, env="Pendulum-v1", n_envs: int = 1, n_timesteps: int = 1000,
+                         max_pathlength: int = 1000, seed: int = 1, train: bool = True,
+                         time_limit: Optional[int] = None, reset_uniforms=None, action_normals=None,
+                         max_episodes_per_env: int = 0):
+        """rollout() of a continuous-action environment (a name of CONT_ENVS) under this Gaussian engine's policy:
+        the engine's obs_dim and n_actions must be the environment's obs_dim and act_dim.  train=True samples
+        a = float32(mean + exp(logstd) * normal), train=False acts with the mean.  time_limit=None is the
+        environment's own; injected reset_uniforms are [n_envs, max_episodes_per_env, reset_draws], injected
+        action_normals [n_envs, ceil(n_timesteps/n_envs) + min(max_pathlength, time_limit) - 1, act_dim] standard
+        normals.  Returns (total steps, number of paths)."""
+        cid = _cont_env_id(env)
+        p = _lib.RolloutParams()
+        check(lib.trpo_default_rollout_params_cont(cid, ctypes.byref(p)), "trpo_default_rollout_params_cont")
+        p.n_envs, p.n_timesteps, p.max_pathlength = int(n_envs), int(n_timesteps), int(max_pathlength)
+        p.seed, p.train = int(seed) & ((1 << 64) - 1), int(bool(train))
+        if time_limit is not None:
+            p.time_limit = int(time_limit)
+        keep = []
+        if reset_uniforms is not None:
+            ru = _Arg(reset_uniforms, np.float64)
+            keep.append(ru)
+            p.reset_uniforms = ru.ptr
+            p.max_episodes_per_env = int(max_episodes_per_env)
+            p.mem = ru.mem
+        if action_normals is not None:
+            an = _Arg(action_normals, np.float64)
+            keep.append(an)
+            p.action_uniforms = an.ptr
+            p.mem = an.mem
+        n, paths = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib.trpo_rollout_gaussian(self._h, cid, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
+              "trpo_rollout_gaussian")
+        self.rollout_steps, self.rollout_paths = n.value, paths.value
+        self._tail_ptr = None
+        self.rollout_state_dim = cont_env_info(cid)["state_dim"]
+        return n.value, paths.value
+
+    def rollout_gaussian_fetch(self):
+        """The concatenated Gaussian rollout (host arrays): obs f64 [N,obs_dim] and obs32, actions and means f32
+        [N,A], logstd f32 [A] (what the rollout sampled with), rewards f64, starts u8, normals f64 [N,A] (zeros for
+        train=False) and env_states f64 [N,state_dim]."""
+        if getattr(self, "rollout_steps", None) is None:
+            # no rollout yet: the engine reports the state error
+            check(lib.trpo_rollout_gaussian_fetch(self._h, None, None, None, None, None, None, None, None, None,
+                                                  MEM_HOST), "trpo_rollout_gaussian_fetch")
+        N, A = self.rollout_steps, self.n_actions
+        out = {"obs": np.empty((N, self.obs_dim)), "obs32": np.empty((N, self.obs_dim), np.float32),
+               "actions": np.empty((N, A), np.float32), "means": np.empty((N, A), np.float32),
+               "logstd": np.empty(A, np.float32), "rewards": np.empty(N), "starts": np.empty(N, np.uint8),
+               "normals": np.empty((N, A)), "env_states": np.empty((N, getattr(self, "rollout_state_dim", 1)))}
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        check(lib.trpo_rollout_gaussian_fetch(self._h, *(ptr(out[k]) for k in (
+            "obs", "obs32", "actions", "means", "logstd", "rewards", "starts", "normals", "env_states")), MEM_HOST),
+            "trpo_rollout_gaussian_fetch")
+        return out
+
+    def rollout_gaussian_fetch_ends(self):
+        """rollout_fetch_ends of a Gaussian rollout: truncated, final_obs, final_means f32 [P,A] (the policy's mean
+        at float32(s_T) for cut-off paths, zeros otherwise), lengths, end_rows."""
+        if getattr(self, "rollout_paths", None) is None:
+            check(lib.trpo_rollout_gaussian_fetch_ends(self._h, None, None, None, None, None, MEM_HOST),
+                  "trpo_rollout_gaussian_fetch_ends")
+        P = self.rollout_paths
+        out = {"truncated": np.empty(P, np.uint8), "final_obs": np.empty((P, self.obs_dim)),
+               "final_means": np.empty((P, self.n_actions), np.float32), "lengths": np.empty(P, np.int64),
+               "end_rows": np.empty(P, np.int64)}
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        check(lib.trpo_rollout_gaussian_fetch_ends(self._h, ptr(out["truncated"]), ptr(out["final_obs"]),
+                                                   ptr(out["final_means"]), ptr(out["lengths"]),
+                                                   ptr(out["end_rows"]), MEM_HOST),
+              "trpo_rollout_gaussian_fetch_ends")
+        return out
+
+    def rollout_gaussian_to_batch(self, n_global: Optional[int] = None):
+        """Load the Gaussian rollout as the feed (states, actions, old mean, the rollout's logstd, rewards, path
+        starts) on the device."""
+        N = getattr(self, "rollout_steps", None) or 0
+        ng = N if n_global is None else int(n_global)
+        check(lib.trpo_rollout_gaussian_to_batch(self._h, ng), "trpo_rollout_gaussian_to_batch")
+        self.n, self.n_global = N, ng
         self._tail_ptr = None
 
     # ------------------------------------------------------------------ profiling
@@ -633,6 +746,24 @@ def env_step_device(env, state, action):
     rw, dn = np.empty(n), np.empty(n, np.uint8)
     ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
     check(lib.trpo_env_step(eid, ptr(s), ptr(a), n, ptr(so), ptr(ob), ptr(rw), ptr(dn), MEM_HOST), "trpo_env_step")
+    return so, ob, rw, dn.astype(bool)
+
+
+def cont_env_step_device(env, state, action):
+    """env_step_device for a continuous-action environment: action [n, act_dim] float32 (the components the
+    policy produced).  Returns (state_out [n, state_dim], obs [n, obs_dim], reward [n], done [n] bool)."""
+    cid = _cont_env_id(env)
+    info = cont_env_info(cid)
+    s = np.ascontiguousarray(state, np.float64).reshape(-1, info["state_dim"])
+    a = np.ascontiguousarray(action, np.float32).reshape(-1, info["act_dim"])
+    n = s.shape[0]
+    if a.shape[0] != n:
+        raise ValueError(f"{n} states but {a.shape[0]} actions")
+    so, ob = np.empty((n, info["state_dim"])), np.empty((n, info["obs_dim"]))
+    rw, dn = np.empty(n), np.empty(n, np.uint8)
+    ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    check(lib.trpo_cont_env_step(cid, ptr(s), ptr(a), n, ptr(so), ptr(ob), ptr(rw), ptr(dn), MEM_HOST),
+          "trpo_cont_env_step")
     return so, ob, rw, dn.astype(bool)
 
 
