@@ -322,6 +322,9 @@ int trpo_gae(const double* rewards, const double* values, const uint8_t* episode
  * planes, hi and lo, in the bytes of the f32 matrix, and its readers, rbwd0's epilogue and the layer-1 weight
  * gradient, fetch the hi plane alone where their "low_seg" test fires and both planes where it does not:
  * 1 = on, the default; 0 = RH_1 in f32, every launch and every bit as without the option).
+ * "rbwd0_bdma" (rbwd0.hip's k-loop: the pre-split weight planes reach LDS by LDS-DMA, a ring of three 32-KB
+ * slots, instead of through registers; the same planes, products and order, so bit-identical: 1 = on, the
+ * default; 0 = register-staged).
  * "ls_fused" = 2 mixes two forwards inside one line search (loss_before from the per-layer forward, the
  * trials' losses from fwd_loss16); it exists for A/B timing and is held to the same parity tests.
  * Rejected variants (other tiles, last-layer fusions, 16-bit E planes, a second stream) were removed

@@ -54,6 +54,8 @@ struct Options {
                        // row-paired f16 hi / lo planes (PairPlane below); its readers, the layer-1 weight gradient
                        // and the fused R-backward's epilogue, fetch the hi plane alone where their low_seg test
                        // fires and both planes where it does not: 1 (default) on, 0 off
+  int rbwd0_bdma;      // rbwd0.hip: the k-loop's weight planes reach LDS by LDS-DMA into a ring of three slots
+                       // instead of through registers (bit-identical): 1 (default) on, 0 off
 };
 
 // A running-max slot is kAmaxSub counters, each on its own 128-B line: producers reduce within the

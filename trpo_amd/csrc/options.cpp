@@ -37,6 +37,7 @@ constexpr OptionRow kOptionRows[] = {
     {"rfwd01", "TRPO_RFWD01", &Options::rfwd01, 1},
     {"fwd01", "TRPO_FWD01", &Options::fwd01, 1},
     {"rh1_planes", "TRPO_RH1_PLANES", &Options::rh1_planes, 1},
+    {"rbwd0_bdma", "TRPO_RBWD0_BDMA", &Options::rbwd0_bdma, 1},
 };
 static_assert(sizeof kOptionRows / sizeof kOptionRows[0] == sizeof(Options) / sizeof(int),
               "every field of Options needs a row");

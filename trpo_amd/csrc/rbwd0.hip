@@ -19,7 +19,10 @@
 //     4 rows 16s + 8t + 4h .. +3 of column m, the matching A operand.  The image arrives by LDS-DMA
 //     (buffer_load ... lds) at the start of each tile, overlapped with the k-loop.
 //   * k-loop: the register-staged f16 split of rowgemm3_kernel (A split on the way to LDS, B from the
-//     engine's pre-split weight planes), BK = 32 (R0_BK), two k-tiles of loads in flight.
+//     engine's pre-split weight planes), BK = 32 (R0_BK), two k-tiles of loads in flight.  Under option
+//     rbwd0_bdma (BD) the weight planes, on which nothing is computed on the way, go to LDS by LDS-DMA into a ring
+//     of three slots instead (the swizzle in the lanes' source offsets); A stays register-staged.  The kernel
+//     counts the DMAs' completions itself (dstep).  C4: fvp_rbwdwg_l1 10.00 -> 9.35 ms (profiles/r8bdma).
 //   * Scales: when segment 1 (D_1 V_1^T) sits >= low_seg binades under segment 0 (rbwd0_sw, the C4 case) its
 //     tiles run first on one product from D_1's f16 hi plane at the plane's own scale, and the accumulator
 //     then steps down by an exact power of two to segment 0's; otherwise the two segments share one product
@@ -85,6 +88,14 @@ constexpr bool kR0XAlias = (2 * kR0STG + 2 * kR0XPL) * 2 + 64 > 160 * 1024;   //
 constexpr int kR0LDSU = kR0XAlias ? (2 * kR0STG > 2 * kR0XPL ? 2 * kR0STG : 2 * kR0XPL) : 2 * kR0STG + 2 * kR0XPL;
 static_assert(kR0LDSU * 2 <= 160 * 1024, "rbwd0 LDS");
 static_assert(kR0BK == 16 || kR0BK == 32, "rbwd0 k-tile");
+// The B operand by LDS-DMA (option rbwd0_bdma, template value BD): the two register-staged A stages, then a ring
+// of three B slots (hi + lo plane images, the layout swzk gives them): 2 x 16 KB + 3 x 32 KB = 128 KB, the X
+// image (64 KB) in the same bytes after the k-loop.  Built for 64-B staged rows and two A stages in flight.
+constexpr int kR0ASTG = 2 * kR0APL;           // u16 per A stage (hi + lo)
+constexpr int kR0BSLOT = 2 * kR0BPL;          // u16 per B ring slot (hi + lo)
+constexpr int kR0LDSD = 2 * kR0ASTG + 3 * kR0BSLOT;
+constexpr bool kR0Dma = kR0BK == 32 && R0_PF == 2 && kR0XAlias && kR0NW == 8 && kR0LDSD >= 2 * kR0XPL &&
+                        kR0LDSD * 2 + 64 <= 160 * 1024;
 
 // u16 offset of the 16-B chunk c (8 k) of row r in a staged [row][kR0BK] f16 image: 32-B rows flip their two
 // chunks on row bit 2 ^ bit 3 (swz16), 64-B rows XOR theirs with row bits 2-3 (plane.hip's pl_swz); both keep
@@ -110,7 +121,8 @@ __device__ __forceinline__ int xoff(int row, int ch) {
 // variants are separate instantiations so neither carries the other's live ranges
 // RP: RH_1 from the f32 matrix (0), from its hi plane (1: the low_seg test fired, SW bodies) or (2: the bodies
 // without D_1's plane) from its hi plane where the test fired and from hi + lo where it did not, decided per launch
-template <int NSEG, bool SW, int RP>
+// BD: the k-loop's B operand by LDS-DMA into a ring of three slots (option rbwd0_bdma) instead of through registers
+template <int NSEG, bool SW, int RP, bool BD>
 __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* smem, float* sMax) {
   constexpr bool kE = NSEG == 2;
   constexpr int TM = kR0TM, CT = kR0CT;
@@ -207,13 +219,15 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
       for (int j = 0; j < CT; ++j) acc[i][j] = f32x16{};
     struct Stage {
       f32x4 ra[kR0AI];
-      u16x8 rb[kR0BI];
+      u16x8 rb[BD ? 1 : kR0BI];   // BD: B never passes through registers
     };
     // tile t: segment 1 is tiles [0, nk) under sw, [nk, 2 nk) otherwise; pt = a D_1 hi-plane tile
-    auto gload = [&](Stage& st, int t) {
+    // ptc: whether the tile is a plane tile, known where the call is made (BD's steps: 0 / 1) or not (-1)
+    using PtRt = std::integral_constant<int, -1>;
+    auto gload_as = [&](Stage& st, int t, auto ptc) {
       // segment 1 exists only for NSEG == 2 (compile time): a one-segment launch never forms an A1 / B1
       // address, whatever tile index reaches here
-      const bool pt = sw && t < nk;
+      const bool pt = decltype(ptc)::value < 0 ? sw && t < nk : decltype(ptc)::value != 0;
       const bool s1 = NSEG > 1 && (sw ? t < nk : t >= nk);
       const int kt = (NSEG > 1 && t >= nk) ? t - nk : t;
       const int k0 = kt * kR0BK;
@@ -233,6 +247,7 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
           st.ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rA, vo, k0 * 4, 0));
         }
       }
+      if constexpr (BD) return;
       const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)(s1 ? A.B1 : A.B0), 0, bbytes,
                                                                           0x00020000);
 #pragma unroll
@@ -245,10 +260,11 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
         st.rb[i] = __builtin_bit_cast(u16x8, __builtin_amdgcn_raw_buffer_load_b128(rB, vo, k0 * 2, 0));
       }
     };
-    auto sstore = [&](const Stage& st, int buf, int t) {
-      unsigned short* As = smem + buf * kR0STG;
+    auto gload = [&](Stage& st, int t) { gload_as(st, t, PtRt{}); };
+    auto sstore_as = [&](const Stage& st, int buf, int t, auto ptc) {
+      unsigned short* As = smem + buf * (BD ? kR0ASTG : kR0STG);
       unsigned short* Bs = As + 2 * kR0APL;
-      const bool pt = sw && t < nk;
+      const bool pt = decltype(ptc)::value < 0 ? sw && t < nk : decltype(ptc)::value != 0;
       const float sa = (NSEG > 1 && (sw ? t < nk : t >= nk)) ? sA1 : sA0;   // segment 1's scale (not read on pt)
       if (pt) *reinterpret_cast<u16x8*>(As + swzk(tid >> 2, tid & 3)) = __builtin_bit_cast(u16x8, st.ra[0]);
       else
@@ -267,6 +283,7 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
         *reinterpret_cast<u16x4*>(dst) = h;
         *reinterpret_cast<u16x4*>(dst + kR0APL) = l;
       }
+      if constexpr (BD) return;
 #pragma unroll
       for (int i = 0; i < kR0BI; ++i) {
         if (pt && i >= kR0BI / 2) break;
@@ -275,10 +292,12 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
         *reinterpret_cast<u16x8*>(Bs + p * kR0BPL + swzk(rem / CB, rem % CB)) = st.rb[i];
       }
     };
-    auto compute = [&](int buf, auto one_c) {
+    auto sstore = [&](const Stage& st, int buf, int t) { sstore_as(st, buf, t, PtRt{}); };
+    // buf: the A stage; bslot: the B ring slot (BD; the register-staged B sits behind its stage's A)
+    auto compute = [&](int buf, int bslot, auto one_c) {
       constexpr bool one = decltype(one_c)::value;
-      const unsigned short* As = smem + buf * kR0STG;
-      const unsigned short* Bs = As + 2 * kR0APL;
+      const unsigned short* As = smem + buf * (BD ? kR0ASTG : kR0STG);
+      const unsigned short* Bs = BD ? smem + 2 * kR0ASTG + bslot * kR0BSLOT : As + 2 * kR0APL;
 #pragma unroll
       for (int ks = 0; ks < kR0BK / 16; ++ks) {   // 16-k MFMA steps of the staged k-tile
         f16x8 bh[CT], bl[CT];
@@ -333,19 +352,19 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
         for (int t = tb; t < te; t += 4) {
           // steps past the last k-tile (ntiles % 4 != 0) only keep the load pattern (uniform branches)
           gload(S0, cl(t + 4));
-          compute(0, one_c);
+          compute(0, 0, one_c);
           if (t + 1 < ntiles) sstore(S1, 1, t + 1);
           lds_barrier();
           gload(S1, cl(t + 5));
-          if (t + 1 < ntiles) compute(1, one_c);
+          if (t + 1 < ntiles) compute(1, 0, one_c);
           if (t + 2 < ntiles) sstore(S2, 0, t + 2);
           lds_barrier();
           gload(S2, cl(t + 6));
-          if (t + 2 < ntiles) compute(0, one_c);
+          if (t + 2 < ntiles) compute(0, 0, one_c);
           if (t + 3 < ntiles) sstore(S3, 1, t + 3);
           lds_barrier();
           gload(S3, cl(t + 7));
-          if (t + 3 < ntiles) compute(1, one_c);
+          if (t + 3 < ntiles) compute(1, 0, one_c);
           if (t + 4 < ntiles) sstore(S0, 0, t + 4);
           lds_barrier();
         }
@@ -353,18 +372,114 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
 #else
       // two k-tiles of loads in flight
       Stage S0, S1;
-      gload(S0, 0);
-      gload(S1, ntiles > 1 ? 1 : 0);
-      sstore(S0, 0, 0);
-      lds_barrier();
+      // ---- BD: k-tile t's B image lands in ring slot t % 3 by LDS-DMA, straight from the pre-split planes.  One
+      // instruction moves a 1-KB piece: 16 columns n of one plane, lane l the 16 B at (row n0 + l / 4, slot l % 4)
+      // of the image, which swzk assigns chunk (l % 4) ^ ((n >> 2) & 3) = (l % 4) ^ ((l >> 4) & 3) of column n's
+      // k-tile (n0 is a multiple of 16): the permutation sits in the lane's source offset.  Wave w moves pieces
+      // 2 w, 2 w + 1 of the hi plane and, on three-product tiles, of the lo plane.  Columns >= Npad (whole pieces:
+      // Npad is a multiple of 32) and chunks at k >= ldk take an offset past the descriptor and land as zeros.
+      const int cB = (lane & 3) ^ ((lane >> 4) & 3);
+      const int vb = ((lane >> 2) * A.ldk + 8 * cB) * 2;
+      const unsigned lds_b = (unsigned)(uintptr_t)(smem + 2 * kR0ASTG);
+      auto bdma = [&](int t, int slot, auto ptc) {
+        constexpr bool pt = decltype(ptc)::value != 0;   // a one-product (D_1 plane) tile
+        const bool s1 = NSEG > 1 && (sw ? t < nk : t >= nk);
+        const int k0 = ((NSEG > 1 && t >= nk) ? t - nk : t) * kR0BK;
+        const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)(s1 ? A.B1 : A.B0), 0, bbytes,
+                                                                            0x00020000);
+        const int vk = k0 + 8 * cB < A.ldk ? vb : kOob;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          if (pt && p) break;   // the lo plane is unread on one product
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int q = 2 * wv + j;   // uniform
+            dma16(rB, (unsigned)(16 * q < Npad ? vk : kOob),
+                  (unsigned)((p * A.plane + (int64_t)16 * q * A.ldk + k0) * 2),
+                  lds_b + (unsigned)((slot * kR0BSLOT + p * kR0BPL) * 2 + q * 1024));
+          }
+        }
+      };
+      // One step of the DMA form: tile t from A stage `buf` (= t & 1) and B slot sb (= t % 3).  The kinds of tile t
+      // (one_c: one product), t + 1 (spt: its A stage is D_1's plane) and t + 2 (lpt) are compile-time values: as
+      // runtime branches they merged the two kinds' register loads behind waits that hipcc, which does not see the
+      // DMAs, sized to drain them.  VMEM issue order of a step: B(t + 2)'s DMAs (4; 2 on a one-product tile; none
+      // past the last tile), then A(t + 2)'s register loads (2; 1 from the plane), pinned by the scheduling barrier
+      // between them.  Slot (t + 2) % 3 was last read by compute(t - 1), which every wave left at the previous
+      // step's barrier.  Completions retire in issue order, so "B(t + 1) has landed" is "at most the operations
+      // issued after B(t + 1)'s DMAs are outstanding": B(t + 2)'s DMAs and A(t + 2)'s loads (A(t + 1)'s loads are
+      // not counted: hipcc may place them on either side of B(t + 1)'s DMAs).  That is 2 + 1 = 3 where tile t + 2
+      // is one-product, 4 + 2 = 6 where it is not, and 2 once t + 2 is past the last tile.  A smaller count than the
+      // true one only waits longer; none is larger.  After the last step's vmcnt(2) no DMA is in flight: the X
+      // image may take the ring's bytes.
+      auto dstep = [&](int t, auto buf_c, auto one_c, auto spt, auto lpt, int& sb) {
+        constexpr int buf = decltype(buf_c)::value;
+        if (t + 2 < ntiles) bdma(t + 2, sb == 0 ? 2 : sb - 1, lpt);
+        __builtin_amdgcn_sched_barrier(0);
+        gload_as(buf ? S1 : S0, t + 2 < ntiles ? t + 2 : ntiles - 1, lpt);   // unconditional: a uniform count
+        __builtin_amdgcn_sched_barrier(0);
+        if (t < ntiles) compute(buf, sb, one_c);
+        // unconditional too (past the last tile it re-stores that tile into the stage nobody reads again): a path
+        // around it would leave its registers' loads unconsumed, and hipcc's wait for them at the next loads into
+        // the same registers, sized without the DMAs, would drain the DMAs just issued
+        sstore_as(buf ? S0 : S1, buf ^ 1, t + 1, spt);
+        __builtin_amdgcn_sched_barrier(0);
+        if (decltype(lpt)::value) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        else if (t + 2 < ntiles) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        lds_barrier();
+        sb = sb == 2 ? 0 : sb + 1;
+      };
+      using I0 = std::integral_constant<int, 0>;
+      using I1 = std::integral_constant<int, 1>;
+      using ISw = std::integral_constant<int, sw>;   // tiles 0 and 1 (sw: nk is even, so >= 2)
+      if constexpr (BD) {
+        // prologue: B(0), B(1) (tile 0 again when there is one tile), then the A loads; B(0) has landed when at
+        // most B(1)'s DMAs (2 one-product, 4 otherwise) are outstanding
+        bdma(0, 0, ISw{});
+        bdma(ntiles > 1 ? 1 : 0, 1, ISw{});
+        __builtin_amdgcn_sched_barrier(0);
+        gload_as(S0, 0, ISw{});
+        gload_as(S1, ntiles > 1 ? 1 : 0, ISw{});
+        sstore_as(S0, 0, 0, ISw{});
+        __builtin_amdgcn_sched_barrier(0);
+        if (sw) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        lds_barrier();
+      } else {
+        gload(S0, 0);
+        gload(S1, ntiles > 1 ? 1 : 0);
+        sstore(S0, 0, 0);
+        lds_barrier();
+      }
+      int sb = 0;   // BD: the ring slot of the step's tile
       auto kloop = [&](int tb, int te, auto one_c) {
+        if constexpr (BD) {
+          if constexpr (decltype(one_c)::value) {
+            // one-product tiles [0, nk): the last two steps load, and the last one stores, three-product tiles
+            for (int t = tb; t < te - 2; t += 2) {
+              dstep(t, I0{}, one_c, I1{}, I1{}, sb);
+              dstep(t + 1, I1{}, one_c, I1{}, I1{}, sb);
+            }
+            if (tb < te) {
+              dstep(te - 2, I0{}, one_c, I1{}, I0{}, sb);
+              dstep(te - 1, I1{}, one_c, I0{}, I0{}, sb);
+            }
+          } else {
+            for (int t = tb; t < te; t += 2) {
+              dstep(t, I0{}, one_c, I0{}, I0{}, sb);
+              dstep(t + 1, I1{}, one_c, I0{}, I0{}, sb);
+            }
+          }
+          return;
+        }
         for (int t = tb; t < te; t += 2) {
           gload(S0, t + 2 < ntiles ? t + 2 : ntiles - 1);   // unconditional: keeps vmcnt counting exact
-          compute(0, one_c);
+          compute(0, 0, one_c);
           if (t + 1 < ntiles) sstore(S1, 1, t + 1);
           lds_barrier();
           gload(S1, t + 3 < ntiles ? t + 3 : ntiles - 1);
-          if (t + 1 < ntiles) compute(1, one_c);
+          if (t + 1 < ntiles) compute(1, 0, one_c);
           if (t + 2 < ntiles) sstore(S0, 0, t + 2);
           lds_barrier();
         }
@@ -564,6 +679,8 @@ __device__ __forceinline__ void rbwd0_body(const RBwd0Args& A, unsigned short* s
     const float bt = xadd_f<true>(bsum[tn]);   // the two lane halves' rows, same order on both
     if (lh == 0 && j < A.N) out[A.dst.off_b + j] = bt;
   }
+  // no DMA may land after the workgroup has left the CU (none is in flight past a tile's k-loop; belt and braces)
+  if constexpr (BD) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // the launch's low_seg verdict: segment 1 (and with it every O(eps) KL_ff operand) >= low_seg binades under
@@ -582,24 +699,33 @@ __device__ __forceinline__ bool rbwd0_sw(const RBwd0Args& A, bool one1) {
 }
 
 // PL: RH_1 comes as planes (a kernel of its own: four bodies in one kernel doubled its scalar spills)
-template <int NSEG, bool PL = false>
+// BD: the B operand by LDS-DMA (option rbwd0_bdma; kernels of their own, so the two forms compare in one process)
+template <int NSEG, bool PL = false, bool BD = false>
 __global__ void __launch_bounds__(kR0NT, 1) rbwd0_kernel(const RBwd0Args A) {
-  __shared__ __attribute__((aligned(16))) unsigned short smem[kR0LDSU];
+  __shared__ __attribute__((aligned(16))) unsigned short smem[BD ? kR0LDSD : kR0LDSU];
   __shared__ float sMax[kR0NW];
   if (A.skip && *A.skip) return;
   if constexpr (NSEG > 1) {
     const bool one1 = rbwd0_one1(A), sw = rbwd0_sw(A, one1);
     if constexpr (PL) {
-      if (sw) rbwd0_body<NSEG, true, 1>(A, smem, sMax);
-      else rbwd0_body<NSEG, false, 2>(A, smem, sMax);
+      if (sw) rbwd0_body<NSEG, true, 1, BD>(A, smem, sMax);
+      else rbwd0_body<NSEG, false, 2, BD>(A, smem, sMax);
       return;
     }
     if (sw) {
-      rbwd0_body<NSEG, true, 0>(A, smem, sMax);
+      rbwd0_body<NSEG, true, 0, BD>(A, smem, sMax);
       return;
     }
   }
-  rbwd0_body<NSEG, false, 0>(A, smem, sMax);
+  rbwd0_body<NSEG, false, 0, BD>(A, smem, sMax);
+}
+
+template <bool BD>
+void rbwd0_launch(const RBwd0Args& b, bool planes, hipStream_t s) {
+  const dim3 g(b.dst.splits), t(kR0NT);
+  if (b.nseg == 2 && planes) hipLaunchKernelGGL((rbwd0_kernel<2, true, BD>), g, t, 0, s, b);
+  else if (b.nseg == 2) hipLaunchKernelGGL((rbwd0_kernel<2, false, BD>), g, t, 0, s, b);
+  else hipLaunchKernelGGL((rbwd0_kernel<1, false, BD>), g, t, 0, s, b);
 }
 
 }  // namespace
@@ -628,9 +754,14 @@ void launch_rbwd0(const RBwd0Args& a, hipStream_t s) {
     b.am_a1 = b.am_a0;
     b.am_b1 = b.am_b0;
   }
-  if (a.nseg == 2 && a.RHp.hi) hipLaunchKernelGGL((rbwd0_kernel<2, true>), dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
-  else if (a.nseg == 2) hipLaunchKernelGGL(rbwd0_kernel<2>, dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
-  else hipLaunchKernelGGL(rbwd0_kernel<1>, dim3(a.dst.splits), dim3(kR0NT), 0, s, b);
+  // the DMA form exists in the shipped tile geometry (64-B staged rows, two A stages); other builds keep B in registers
+  if constexpr (kR0Dma) {
+    if (g_options.rbwd0_bdma != 0) {
+      rbwd0_launch<true>(b, a.RHp.hi != nullptr, s);
+      return;
+    }
+  }
+  rbwd0_launch<false>(b, a.RHp.hi != nullptr, s);
 }
 
 }  // namespace trpo
