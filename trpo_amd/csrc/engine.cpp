@@ -314,11 +314,11 @@ struct trpo_engine {
     double* obs = nullptr;
     double* env_state = nullptr;   // [rows][state_cap]; only for an environment whose observation is not its state
     int state_cap = 0;
-    int64_t* actions = nullptr;
+    int64_t* actions = nullptr;   // categorical
     float* dist = nullptr;
+    double* noise = nullptr;      // [rows] cat_sample uniforms, or (Gaussian) [rows][A] normals
     double* rewards = nullptr;
     uint8_t* starts = nullptr;
-    double* uniforms = nullptr;
     int64_t *counts = nullptr, *episodes = nullptr, *offsets = nullptr;
     double *reset_u = nullptr, *act_u = nullptr;
     int64_t reset_u_n = 0, act_u_n = 0;
@@ -333,13 +333,11 @@ struct trpo_engine {
     float *cat_obs32 = nullptr, *cat_dist = nullptr;
     int64_t *cat_len = nullptr, *cat_rows = nullptr;
     // a Gaussian engine's rollout (trpo_rollout_gaussian): dist, end_dist and cat_dist hold means; the actions
-    // [rows][A] f32, the normals [rows][A] and the log-std vector [A] the rollout sampled with
+    // [rows][A] f32 and the log-std vector [A] the rollout sampled with
     float* actf = nullptr;
-    double* normals = nullptr;
     float* logstd = nullptr;
   } roll;
-  RolloutArgs roll_args{};
-  GaussRolloutArgs groll_args{};   // the last rollout of a Gaussian engine (roll_valid)
+  RolloutArgs roll_args{};   // the last rollout (roll_valid)
   int64_t roll_n = 0, roll_paths = 0, roll_maxcount = 0, roll_maxpaths = 0;
   bool roll_valid = false;
   bool feed_is_rollout = false;   // the feed is the one trpo_rollout_to_batch loaded (trpo_get_tail_view)
@@ -690,17 +688,23 @@ struct trpo_engine {
     return static_cast<T*>(ptr);
   }
 
-  // rollout (utils.py:18-45) of n_envs instances of a built-in environment under the current policy
-  void rollout(int env, const trpo_rollout_params& p) {
+  // rollout (utils.py:18-45) of n_envs instances of a built-in environment under the current policy: an environment
+  // of TRPO_ENV_* under the categorical head, or (continuous) of TRPO_CENV_* under the Gaussian one.  Every check
+  // comes before anything of the previous rollout is freed or overwritten, so a refused call leaves it fetchable.
+  // A Gaussian rollout copies the log-std vector aside first: it samples with the copy, and the feed built from it
+  // (trpo_rollout_gaussian_to_batch) takes it as the old log-std whatever theta has become since.
+  void rollout(bool continuous, int env, const trpo_rollout_params& p) {
     EnvDims ed{};
-    REQUIRE(env_dims(env, &ed), "unknown environment id " + std::to_string(env));
+    REQUIRE(env_dims(continuous, env, &ed),
+            std::string(continuous ? "unknown continuous environment id " : "unknown environment id ") +
+                std::to_string(env));
     REQUIRE(p.n_envs >= 1 && p.n_envs <= (1 << 20), "n_envs out of range");
     REQUIRE(p.n_timesteps >= 1 && p.max_pathlength >= 1 && p.time_limit >= 1, "bad rollout lengths");
-    REQUIRE(w[0] == ed.obs_dim && w[L] == ed.n_actions,
-            std::string(ed.name) + " needs obs_dim " + std::to_string(ed.obs_dim) + " and " +
-                std::to_string(ed.n_actions) + " actions; the engine has obs_dim " + std::to_string(w[0]) + " and " +
-                std::to_string(w[L]) + " actions");
-    const int obs_dim = ed.obs_dim, A = ed.n_actions;
+    auto head = [&](int n) { return continuous ? "act_dim " + std::to_string(n) : std::to_string(n) + " actions"; };
+    REQUIRE(w[0] == ed.obs_dim && w[L] == ed.head_dim,
+            std::string(ed.name) + " needs obs_dim " + std::to_string(ed.obs_dim) + " and " + head(ed.head_dim) +
+                "; the engine has obs_dim " + std::to_string(w[0]) + " and " + head(w[L]));
+    const int obs_dim = ed.obs_dim, A = ed.head_dim, noise_dim = continuous ? A : 1;
     const int state_cap = ed.state_dim == ed.obs_dim ? 0 : ed.state_dim;   // such environments observe the state itself
     const int ep_max = std::min(p.max_pathlength, p.time_limit);
     const int64_t budget = (p.n_timesteps + p.n_envs - 1) / p.n_envs;
@@ -708,7 +712,13 @@ struct trpo_engine {
     const int64_t rows = env_cap * p.n_envs;
     REQUIRE(rows <= (int64_t(1) << 34), "rollout too large");
     const int64_t paths = budget * p.n_envs;   // every episode has at least one step
-    feed_is_rollout = false;                   // the end records of the loaded feed are about to be overwritten
+    if (p.reset_uniforms) {
+      REQUIRE(p.max_episodes_per_env >= 1, "max_episodes_per_env required with reset_uniforms");
+      // every episode an environment can start must have its uniforms
+      REQUIRE((int64_t)p.max_episodes_per_env >= budget, "max_episodes_per_env must be >= ceil(n_timesteps/n_envs)");
+    }
+    feed_is_rollout = false;   // the end records of the loaded feed and the regions are about to be overwritten
+    roll_valid = false;
     if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths || state_cap > roll.state_cap) {
       for (void* ptr : roll.mem) HIPCHECK(hipFree(ptr));
       roll = RollBufs{};
@@ -728,20 +738,27 @@ struct trpo_engine {
       roll.obs = ralloc<double>((size_t)rows * obs_dim);
       roll.state_cap = state_cap;
       if (state_cap) roll.env_state = ralloc<double>((size_t)rows * state_cap);
-      roll.actions = ralloc<int64_t>(rows);
       roll.dist = ralloc<float>((size_t)rows * A);
+      roll.noise = ralloc<double>((size_t)rows * noise_dim);
+      if (continuous) {
+        roll.actf = ralloc<float>((size_t)rows * A);
+        roll.logstd = ralloc<float>(A);
+      } else {
+        roll.actions = ralloc<int64_t>(rows);
+      }
       roll.rewards = ralloc<double>(rows);
       roll.starts = ralloc<uint8_t>(rows);
-      roll.uniforms = ralloc<double>(rows);
       roll.counts = ralloc<int64_t>(p.n_envs);
       roll.episodes = ralloc<int64_t>(p.n_envs);
       roll.offsets = ralloc<int64_t>((size_t)2 * p.n_envs);
     }
     RolloutArgs a{};
+    a.continuous = continuous;
     a.env = env;
     a.state_dim = ed.state_dim;
     a.ps = policy_shape();
     a.theta = theta;
+    a.logstd = roll.logstd;
     a.maxw = max_width();
     a.n_envs = p.n_envs;
     a.max_pathlength = p.max_pathlength;
@@ -751,7 +768,8 @@ struct trpo_engine {
     a.env_cap = env_cap;
     a.max_episodes = p.max_episodes_per_env;
     a.seed = p.seed;
-    // optional injected uniforms (tests): reset [n_envs][max_episodes][reset_draws], act [n_envs][env_cap]
+    // optional injected draws (tests): reset uniforms [n_envs][max_episodes][reset_draws], and for the act uniforms
+    // [n_envs][env_cap] or (continuous) standard normals [n_envs][env_cap][A]
     auto stage_u = [&](const double* src, int64_t count, double*& buf, int64_t& cap_n) -> const double* {
       if (!src) return nullptr;
       if (p.mem == TRPO_MEM_DEVICE) return src;
@@ -762,26 +780,24 @@ struct trpo_engine {
       copy_in(buf, src, (size_t)count * sizeof(double), TRPO_MEM_HOST);
       return buf;
     };
-    if (p.reset_uniforms) REQUIRE(p.max_episodes_per_env >= 1, "max_episodes_per_env required with reset_uniforms");
     a.reset_u = stage_u(p.reset_uniforms, (int64_t)p.n_envs * std::max(1, p.max_episodes_per_env) * ed.reset_draws,
                         roll.reset_u, roll.reset_u_n);
-    a.act_u = stage_u(p.action_uniforms, rows, roll.act_u, roll.act_u_n);
-    if (a.reset_u) {
-      // every episode an environment can start must have its uniforms
-      REQUIRE((int64_t)p.max_episodes_per_env >= budget, "max_episodes_per_env must be >= ceil(n_timesteps/n_envs)");
-    }
+    a.draws = stage_u(p.action_uniforms, rows * noise_dim, roll.act_u, roll.act_u_n);
+    if (continuous) copy_in(roll.logstd, logstd_of(theta), (size_t)A * sizeof(float), TRPO_MEM_DEVICE);
     a.obs = roll.obs;
     a.env_state = state_cap ? roll.env_state : nullptr;
-    a.actions = roll.actions;
-    a.dist = roll.dist;
+    a.head = roll.dist;
+    a.acti = roll.actions;
+    a.actf = roll.actf;
+    a.noise = roll.noise;
+    a.noise_dim = noise_dim;
     a.rewards = roll.rewards;
     a.starts = roll.starts;
-    a.uniforms_out = roll.uniforms;
     a.counts = roll.counts;
     a.episodes = roll.episodes;
     a.end_truncated = roll.end_truncated;
     a.end_obs = roll.end_obs;
-    a.end_dist = roll.end_dist;
+    a.end_head = roll.end_dist;
     a.end_len = roll.end_len;
     a.end_row = roll.end_row;
     launch_rollout(a, stream);
@@ -819,114 +835,55 @@ struct trpo_engine {
     check_launch();
   }
 
-  // The same rollout of a continuous-action environment under this Gaussian engine's policy (rollout.hip).  The
-  // log-std vector is copied aside first: the rollout samples with the copy, and the feed built from it
-  // (trpo_rollout_gaussian_to_batch) takes it as the old log-std whatever theta has become since.
-  void rollout_gaussian(int cenv, const trpo_rollout_params& p) {
-    ContEnvDims ed{};
-    REQUIRE(cont_env_dims(cenv, &ed), "unknown continuous environment id " + std::to_string(cenv));
-    REQUIRE(p.n_envs >= 1 && p.n_envs <= (1 << 20), "n_envs out of range");
-    REQUIRE(p.n_timesteps >= 1 && p.max_pathlength >= 1 && p.time_limit >= 1, "bad rollout lengths");
-    REQUIRE(w[0] == ed.obs_dim && w[L] == ed.act_dim,
-            std::string(ed.name) + " needs obs_dim " + std::to_string(ed.obs_dim) + " and act_dim " +
-                std::to_string(ed.act_dim) + "; the engine has obs_dim " + std::to_string(w[0]) + " and act_dim " +
-                std::to_string(w[L]));
-    const int obs_dim = ed.obs_dim, A = ed.act_dim;
-    const int state_cap = ed.state_dim == ed.obs_dim ? 0 : ed.state_dim;
-    const int ep_max = std::min(p.max_pathlength, p.time_limit);
-    const int64_t budget = (p.n_timesteps + p.n_envs - 1) / p.n_envs;
-    const int64_t env_cap = budget + ep_max - 1;
-    const int64_t rows = env_cap * p.n_envs;
-    REQUIRE(rows <= (int64_t(1) << 34), "rollout too large");
-    const int64_t paths = budget * p.n_envs;
-    if (p.reset_uniforms) {
-      REQUIRE(p.max_episodes_per_env >= 1, "max_episodes_per_env required with reset_uniforms");
-      REQUIRE((int64_t)p.max_episodes_per_env >= budget, "max_episodes_per_env must be >= ceil(n_timesteps/n_envs)");
-    }
-    feed_is_rollout = false;
-    roll_valid = false;   // the regions are about to be overwritten
-    if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths || state_cap > roll.state_cap) {
-      for (void* ptr : roll.mem) HIPCHECK(hipFree(ptr));
-      roll = RollBufs{};
-      roll.rows = rows;
-      roll.envs = p.n_envs;
-      roll.paths = paths;
-      roll.end_truncated = ralloc<uint8_t>(paths);
-      roll.end_obs = ralloc<double>((size_t)paths * obs_dim);
-      roll.end_dist = ralloc<float>((size_t)paths * A);
-      roll.end_len = ralloc<int64_t>(paths);
-      roll.end_row = ralloc<int64_t>(paths);
-      roll.cat_truncated = ralloc<uint8_t>(paths);
-      roll.cat_obs32 = ralloc<float>((size_t)paths * obs_dim);
-      roll.cat_dist = ralloc<float>((size_t)paths * A);
-      roll.cat_len = ralloc<int64_t>(paths);
-      roll.cat_rows = ralloc<int64_t>(paths);
-      roll.obs = ralloc<double>((size_t)rows * obs_dim);
-      roll.state_cap = state_cap;
-      if (state_cap) roll.env_state = ralloc<double>((size_t)rows * state_cap);
-      roll.actf = ralloc<float>((size_t)rows * A);
-      roll.dist = ralloc<float>((size_t)rows * A);
-      roll.normals = ralloc<double>((size_t)rows * A);
-      roll.logstd = ralloc<float>(A);
-      roll.rewards = ralloc<double>(rows);
-      roll.starts = ralloc<uint8_t>(rows);
-      roll.counts = ralloc<int64_t>(p.n_envs);
-      roll.episodes = ralloc<int64_t>(p.n_envs);
-      roll.offsets = ralloc<int64_t>((size_t)2 * p.n_envs);
-    }
-    GaussRolloutArgs a{};
-    a.cenv = cenv;
-    a.state_dim = ed.state_dim;
-    a.ps = policy_shape();
-    a.theta = theta;
-    a.logstd = roll.logstd;
-    a.maxw = max_width();
-    a.n_envs = p.n_envs;
-    a.max_pathlength = p.max_pathlength;
-    a.time_limit = p.time_limit;
-    a.train = p.train;
-    a.budget = budget;
-    a.env_cap = env_cap;
-    a.max_episodes = p.max_episodes_per_env;
-    a.seed = p.seed;
-    // optional injected draws (tests): reset uniforms [n_envs][max_episodes][reset_draws], normals [n_envs][env_cap][A]
-    auto stage_u = [&](const double* src, int64_t count, double*& buf, int64_t& cap_n) -> const double* {
-      if (!src) return nullptr;
-      if (p.mem == TRPO_MEM_DEVICE) return src;
-      if (count > cap_n) {
-        buf = ralloc<double>(count);
-        cap_n = count;
-      }
-      copy_in(buf, src, (size_t)count * sizeof(double), TRPO_MEM_HOST);
-      return buf;
-    };
-    a.reset_u = stage_u(p.reset_uniforms, (int64_t)p.n_envs * std::max(1, p.max_episodes_per_env) * ed.reset_draws,
-                        roll.reset_u, roll.reset_u_n);
-    a.act_n = stage_u(p.action_uniforms, rows * A, roll.act_u, roll.act_u_n);
-    HIPCHECK(hipMemcpyAsync(roll.logstd, logstd_of(theta), (size_t)A * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    a.obs = roll.obs;
-    a.env_state = state_cap ? roll.env_state : nullptr;
-    a.actions = roll.actf;
-    a.means = roll.dist;
-    a.normals = roll.normals;
-    a.rewards = roll.rewards;
-    a.starts = roll.starts;
-    a.counts = roll.counts;
-    a.episodes = roll.episodes;
-    a.end_truncated = roll.end_truncated;
-    a.end_obs = roll.end_obs;
-    a.end_mean = roll.end_dist;
-    a.end_len = roll.end_len;
-    a.end_row = roll.end_row;
-    launch_rollout_gaussian(a, stream);
-    check_launch();
-    groll_args = a;
-    rollout_offsets(p.n_envs);
+  // how each path of the last rollout ended, concatenated; final_head is the distribution or the mean at s_T
+  void rollout_fetch_ends(uint8_t* truncated, double* final_obs, float* final_head, int64_t* lengths,
+                          int64_t* end_rows, int mem) {
+    use();
+    const int64_t P = roll_paths;
+    const int obs_dim = w[0], A = w[L];
+    RolloutOut o{};
+    Staging st(mem, stream);
+    o.ends_only = 1;
+    o.path_offsets = roll.path_offsets;
+    o.end_truncated = st.out(truncated, (size_t)P);
+    o.end_obs64 = st.out(final_obs, (size_t)P * obs_dim);
+    o.end_head = st.out(final_head, (size_t)P * A);
+    o.end_len = st.out(lengths, (size_t)P);
+    o.end_rows = st.out(end_rows, (size_t)P);
+    rollout_compact(o);
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(stream));
   }
 
-  void rollout_gaussian_compact(const GaussRolloutOut& o) {
-    launch_rollout_gaussian_compact(groll_args, roll.offsets, o, o.ends_only ? roll_maxpaths : roll_maxcount, stream);
-    check_launch();
+  // the last rollout becomes the feed: `o` names the feed's action column, the rest is the same for both heads
+  void rollout_to_feed(RolloutOut o, int64_t n_glob) {
+    const int64_t N = roll_n;
+    REQUIRE(N <= cap, "rollout has more steps than max_rows");
+    REQUIRE(n_glob >= N, "n_global must be >= the rollout's steps");
+    use();
+    o.X = X;
+    o.ldx = wp[0];
+    o.head = old;
+    o.ld_head = wp[L];
+    o.rewards = rewards;
+    o.starts = starts;
+    // the paths' end records, for trpo_get_tail_view
+    o.path_offsets = roll.path_offsets;
+    o.end_truncated = roll.cat_truncated;
+    o.end_obs32 = roll.cat_obs32;
+    o.end_head = roll.cat_dist;
+    o.end_len = roll.cat_len;
+    o.end_rows = roll.cat_rows;
+    rollout_compact(o);
+    if (gauss()) copy_in(logstd0, roll.logstd, (size_t)w[L] * sizeof(float), TRPO_MEM_DEVICE);
+    n = N;
+    n_global = n_glob;
+    update_x_amax();
+    feed_loaded();
+    feed_is_rollout = true;
+    have_rewards = true;
+    have_baseline = false;
+    HIPCHECK(hipStreamSynchronize(stream));
   }
 
   void release() {
@@ -2788,7 +2745,7 @@ int trpo_rollout_env(trpo_engine* e, int env, const trpo_rollout_params* p, int6
     REQUIRE(e && p, "NULL argument");
     e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_env");
     e->use();
-    e->rollout(env, *p);
+    e->rollout(false, env, *p);
     if (n_steps_out) *n_steps_out = e->roll_n;
     if (n_paths_out) *n_paths_out = e->roll_paths;
   });
@@ -2829,10 +2786,11 @@ int trpo_rollout_fetch(trpo_engine* e, double* obs, float* obs32, int64_t* actio
     o.X = st.out(obs32, (size_t)N * obs_dim);
     o.ldx = obs_dim;
     o.actions64 = st.out(actions, (size_t)N);
-    o.dist = st.out(action_dists, (size_t)N * A);
+    o.head = st.out(action_dists, (size_t)N * A);
+    o.ld_head = A;
     o.rewards = st.out(rewards, (size_t)N);
     o.starts = st.out(episode_starts, (size_t)N);
-    o.uniforms = st.out(uniforms, (size_t)N);
+    o.noise = st.out(uniforms, (size_t)N);
     e->rollout_compact(o);
     st.fetch();
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -2844,36 +2802,9 @@ int trpo_rollout_to_batch(trpo_engine* e, int64_t n_global) {
     REQUIRE(e, "NULL argument");
     e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_to_batch");
     REQUIRE(e->roll_valid, "no rollout to load");
-    const int64_t N = e->roll_n;
-    REQUIRE(N <= e->cap, "rollout has more steps than max_rows");
-    REQUIRE(n_global >= N, "n_global must be >= the rollout's steps");
-    e->use();
     RolloutOut o{};
-    o.X = e->X;
-    o.ldx = e->wp[0];
-    o.old = e->old;
-    o.ld_old = e->wp[e->L];
     o.act32 = e->act;
-    o.rewards = e->rewards;
-    o.starts = e->starts;
-    // the paths' end records, for trpo_get_tail_view
-    o.path_offsets = e->roll.path_offsets;
-    o.end_truncated = e->roll.cat_truncated;
-    o.end_obs32 = e->roll.cat_obs32;
-    o.end_dist = e->roll.cat_dist;
-    o.end_len = e->roll.cat_len;
-    o.end_rows = e->roll.cat_rows;
-    e->rollout_compact(o);
-    e->feed_is_rollout = true;
-    e->n = N;
-    e->n_global = n_global;
-    e->update_x_amax();
-    e->set_splits();
-    e->cache.batch_changed();
-    e->have_rewards = true;
-    e->have_baseline = false;
-    e->have_tail = false;
-    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->rollout_to_feed(o, n_global);
   });
 }
 
@@ -2903,21 +2834,7 @@ int trpo_rollout_fetch_ends(trpo_engine* e, uint8_t* truncated, double* final_ob
     REQUIRE(e, "NULL argument");
     e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_fetch_ends");
     if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
-    e->use();
-    const int64_t P = e->roll_paths;
-    const int obs_dim = e->w[0], A = e->w[e->L];
-    RolloutOut o{};
-    Staging st(mem, e->stream);
-    o.ends_only = 1;
-    o.path_offsets = e->roll.path_offsets;
-    o.end_truncated = st.out(truncated, (size_t)P);
-    o.end_obs64 = st.out(final_obs, (size_t)P * obs_dim);
-    o.end_dist = st.out(final_dists, (size_t)P * A);
-    o.end_len = st.out(lengths, (size_t)P);
-    o.end_rows = st.out(end_rows, (size_t)P);
-    e->rollout_compact(o);
-    st.fetch();
-    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->rollout_fetch_ends(truncated, final_obs, final_dists, lengths, end_rows, mem);
   });
 }
 
@@ -3016,7 +2933,7 @@ int trpo_rollout_gaussian(trpo_engine* e, int cenv, const trpo_rollout_params* p
     e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian");
     REQUIRE(e->w[e->L] <= 64, "rollout_gaussian: act_dim must be <= 64 (one wave per environment)");
     e->use();
-    e->rollout_gaussian(cenv, *p);
+    e->rollout(true, cenv, *p);
     if (n_steps_out) *n_steps_out = e->roll_n;
     if (n_paths_out) *n_paths_out = e->roll_paths;
   });
@@ -3032,20 +2949,20 @@ int trpo_rollout_gaussian_fetch(trpo_engine* e, double* obs, float* obs32, float
     e->use();
     const int64_t N = e->roll_n;
     const int obs_dim = e->w[0], A = e->w[e->L];
-    GaussRolloutOut o{};
+    RolloutOut o{};
     Staging st(mem, e->stream);
     o.obs64 = st.out(obs, (size_t)N * obs_dim);
     o.X = st.out(obs32, (size_t)N * obs_dim);
     o.ldx = obs_dim;
-    o.actions = st.out(actions, (size_t)N * A);
-    o.ld_act = A;
-    o.means = st.out(means, (size_t)N * A);
-    o.ld_mean = A;
-    o.normals = st.out(normals, (size_t)N * A);
+    o.actf = st.out(actions, (size_t)N * A);
+    o.ld_actf = A;
+    o.head = st.out(means, (size_t)N * A);
+    o.ld_head = A;
+    o.noise = st.out(normals, (size_t)N * A);
     o.rewards = st.out(rewards, (size_t)N);
     o.starts = st.out(episode_starts, (size_t)N);
-    o.env_state = st.out(env_states, (size_t)N * e->groll_args.state_dim);
-    e->rollout_gaussian_compact(o);
+    o.env_state = st.out(env_states, (size_t)N * e->roll_args.state_dim);
+    e->rollout_compact(o);
     st.fetch();
     if (logstd) e->copy_out(logstd, e->roll.logstd, (size_t)A * sizeof(float), mem);
     HIPCHECK(hipStreamSynchronize(e->stream));
@@ -3058,21 +2975,7 @@ int trpo_rollout_gaussian_fetch_ends(trpo_engine* e, uint8_t* truncated, double*
     REQUIRE(e, "NULL argument");
     e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian_fetch_ends");
     if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
-    e->use();
-    const int64_t P = e->roll_paths;
-    const int obs_dim = e->w[0], A = e->w[e->L];
-    GaussRolloutOut o{};
-    Staging st(mem, e->stream);
-    o.ends_only = 1;
-    o.path_offsets = e->roll.path_offsets;
-    o.end_truncated = st.out(truncated, (size_t)P);
-    o.end_obs64 = st.out(final_obs, (size_t)P * obs_dim);
-    o.end_mean = st.out(final_means, (size_t)P * A);
-    o.end_len = st.out(lengths, (size_t)P);
-    o.end_rows = st.out(end_rows, (size_t)P);
-    e->rollout_gaussian_compact(o);
-    st.fetch();
-    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->rollout_fetch_ends(truncated, final_obs, final_means, lengths, end_rows, mem);
   });
 }
 
@@ -3081,38 +2984,10 @@ int trpo_rollout_gaussian_to_batch(trpo_engine* e, int64_t n_global) {
     REQUIRE(e, "NULL argument");
     e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian_to_batch");
     if (!e->roll_valid) throw std::runtime_error("no rollout to load");
-    const int64_t N = e->roll_n;
-    REQUIRE(N <= e->cap, "rollout has more steps than max_rows");
-    REQUIRE(n_global >= N, "n_global must be >= the rollout's steps");
-    e->use();
-    const int A = e->w[e->L];
-    GaussRolloutOut o{};
-    o.X = e->X;
-    o.ldx = e->wp[0];
-    o.actions = e->actf;
-    o.ld_act = e->wp[e->L];
-    o.means = e->old;
-    o.ld_mean = e->wp[e->L];
-    o.rewards = e->rewards;
-    o.starts = e->starts;
-    // the paths' end records, for trpo_get_tail_view
-    o.path_offsets = e->roll.path_offsets;
-    o.end_truncated = e->roll.cat_truncated;
-    o.end_obs32 = e->roll.cat_obs32;
-    o.end_mean = e->roll.cat_dist;
-    o.end_len = e->roll.cat_len;
-    o.end_rows = e->roll.cat_rows;
-    e->rollout_gaussian_compact(o);
-    HIPCHECK(hipMemcpyAsync(e->logstd0, e->roll.logstd, (size_t)A * sizeof(float), hipMemcpyDeviceToDevice,
-                            e->stream));
-    e->n = N;
-    e->n_global = n_global;
-    e->update_x_amax();
-    e->feed_loaded();
-    e->feed_is_rollout = true;
-    e->have_rewards = true;
-    e->have_baseline = false;
-    HIPCHECK(hipStreamSynchronize(e->stream));
+    RolloutOut o{};
+    o.actf = e->actf;
+    o.ld_actf = e->wp[e->L];
+    e->rollout_to_feed(o, n_global);
   });
 }
 

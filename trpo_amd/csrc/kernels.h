@@ -780,16 +780,24 @@ struct PolicyShape {
   int w[kMaxLayers + 1];
   int64_t offW[kMaxLayers], offb[kMaxLayers];
 };
-struct EnvDims {            // one built-in environment (TRPO_ENV_*), from its trait in rollout.hip
-  int obs_dim, state_dim, n_actions, reset_draws, time_limit;
+// One built-in environment, from its trait in rollout.hip.  Two id tables: TRPO_ENV_* (discrete actions, rolled out
+// under the categorical head) and, with `continuous`, TRPO_CENV_* (float32 actions, under the diagonal-Gaussian head).
+struct EnvDims {
+  int obs_dim, state_dim;
+  int head_dim;             // A, the policy's output width: the number of actions, or (continuous) act_dim
+  int reset_draws, time_limit;
   const char* name;
 };
-bool env_dims(int env, EnvDims* out);   // host-only; false for an unknown id
+bool env_dims(bool continuous, int env, EnvDims* out);   // host-only; false for an unknown id
+// One rollout kernel serves both heads.  The head row is the action distribution, or (continuous) the mean; the draw
+// of a step is cat_sample's uniform, or (continuous) one standard normal per action component.
 struct RolloutArgs {
-  int env;                  // TRPO_ENV_*; ps must have its obs_dim and n_actions
+  bool continuous;          // which id table `env` is of, and with it the policy head
+  int env;                  // ps must have the environment's obs_dim and head_dim
   int state_dim;            // the environment's
   PolicyShape ps;
   const float* theta;
+  const float* logstd;      // continuous: [A] the log-stds the rollout samples with (the engine's snapshot)
   int maxw;                 // max layer width (LDS slice per wave: 2 * maxw floats)
   int n_envs, max_pathlength, time_limit, train;
   int64_t budget;           // steps per environment: ceil(n_timesteps / n_envs)
@@ -797,21 +805,23 @@ struct RolloutArgs {
   int max_episodes;         // second dim of reset_u
   uint64_t seed;
   const double* reset_u;    // optional [n_envs][max_episodes][reset_draws] uniforms for env.reset
-  const double* act_u;      // optional [n_envs][env_cap] uniforms for cat_sample
+  const double* draws;      // optional [n_envs][env_cap][noise_dim] draws for the act, in place of Philox's
   // per-environment regions (row = env * env_cap + i)
   double* obs;              // [.][obs_dim]
   double* env_state;        // [.][state_dim] the state obs was made from; NULL where the observation is the state
-  int64_t* actions;
-  float* dist;              // [.][A]
+  float* head;              // [.][A]
+  int64_t* acti;            // the action; NULL when continuous
+  float* actf;              // continuous: [.][A] the action
+  double* noise;            // [.][noise_dim] the draw of every step (continuous and train = 0: zeros)
+  int noise_dim;            // 1, or (continuous) A
   double* rewards;
   uint8_t* starts;
-  double* uniforms_out;     // optional: the cat_sample uniform of every step
   int64_t* counts;          // [n_envs] steps collected
   int64_t* episodes;        // [n_envs] episodes collected
   // per-environment path regions (path = env * budget + episode; an environment starts at most budget episodes)
   uint8_t* end_truncated;   // 1: the path was cut off (time limit / max_pathlength), 0: the environment terminated
   double* end_obs;          // [.][obs_dim] the observation of s_T, the state after the path's last step
-  float* end_dist;          // [.][A] the policy's distribution at s_T of a cut-off path, zeros otherwise
+  float* end_head;          // [.][A] the policy's head row at s_T of a cut-off path, zeros otherwise
   int64_t* end_len;         // T, the path's step count
   int64_t* end_row;         // the path's last row within its environment's step region
 };
@@ -820,14 +830,15 @@ struct RolloutOut {         // concatenated outputs; any pointer may be NULL
   double* env_state;        // [N][state_dim]
   float* X;                 // [N][ldx]   (engine batch: f32 states)
   int ldx;
-  float* dist;              // [N][A]
-  float* old;               // [N][ld_old] (engine batch: oldaction_dist)
-  int ld_old;
+  float* head;              // [N][ld_head] (engine batch: oldaction_dist, or the old mean)
+  int ld_head;
   int64_t* actions64;
   int* act32;
+  float* actf;              // [N][ld_actf]
+  int ld_actf;
+  double* noise;            // [N][noise_dim]
   double* rewards;
   uint8_t* starts;
-  double* uniforms;
   // the per-path end records [n_paths], in the order of the concatenated rollout; written when path_offsets
   // ([n_envs] exclusive sums of the episode counts) is given
   const int64_t* path_offsets;
@@ -835,7 +846,7 @@ struct RolloutOut {         // concatenated outputs; any pointer may be NULL
   uint8_t* end_truncated;
   double* end_obs64;        // [n_paths][obs_dim]
   float* end_obs32;
-  float* end_dist;          // [n_paths][A]
+  float* end_head;          // [n_paths][A]
   int64_t* end_len;
   int64_t* end_rows;        // index of the path's last step in the concatenated rollout
 };
@@ -851,76 +862,10 @@ void launch_act(const PolicyShape& ps, const float* theta, int maxw, const float
 void launch_act_gaussian(const PolicyShape& ps, const float* theta, const float* logstd, int maxw, const float* states,
                          int64_t n, const double* normals, int train, float* actions, float* means, hipStream_t s);
 void launch_cat_sample(const float* prob, int64_t n, int k, const double* r, int64_t* out, hipStream_t s);
-void launch_cartpole_step(const double* state, const int64_t* action, int64_t n, double* state_out, double* reward,
-                          uint8_t* done, hipStream_t s);
-// state [n][state_dim] -> state_out, obs_out [n][obs_dim], reward, done (termination); outputs may be NULL
-void launch_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out,
+// state [n][state_dim], action [n] i64 or (continuous) [n][head_dim] f32 -> state_out, obs_out [n][obs_dim], reward,
+// done (termination); outputs may be NULL
+void launch_env_step(bool continuous, int env, const double* state, const void* action, int64_t n, double* state_out,
                      double* obs_out, double* reward, uint8_t* done, hipStream_t s);
-
-// The continuous-action environments (TRPO_CENV_*) under the diagonal-Gaussian policy: the same per-wave rollout
-// with the Gaussian act (launch_act_gaussian's arithmetic) in place of softmax + cat_sample.
-struct ContEnvDims {        // one continuous-action environment, from its trait in rollout.hip
-  int obs_dim, state_dim, act_dim, reset_draws, time_limit;
-  const char* name;
-};
-bool cont_env_dims(int cenv, ContEnvDims* out);   // host-only; false for an unknown id
-struct GaussRolloutArgs {
-  int cenv;                 // TRPO_CENV_*; ps must have its obs_dim and act_dim
-  int state_dim;            // the environment's
-  PolicyShape ps;
-  const float* theta;
-  const float* logstd;      // [A] the log-stds the rollout samples with (the engine's snapshot)
-  int maxw;
-  int n_envs, max_pathlength, time_limit, train;
-  int64_t budget, env_cap;  // as RolloutArgs
-  int max_episodes;
-  uint64_t seed;
-  const double* reset_u;    // optional [n_envs][max_episodes][reset_draws] uniforms for env.reset
-  const double* act_n;      // optional [n_envs][env_cap][A] standard normals for the act
-  // per-environment regions (row = env * env_cap + i)
-  double* obs;              // [.][obs_dim]
-  double* env_state;        // [.][state_dim]; NULL where the observation is the state
-  float* actions;           // [.][A]
-  float* means;             // [.][A]
-  double* normals;          // [.][A] the normal of every action component (0 when train = 0)
-  double* rewards;
-  uint8_t* starts;
-  int64_t* counts;          // [n_envs]
-  int64_t* episodes;        // [n_envs]
-  // per-environment path regions (path = env * budget + episode)
-  uint8_t* end_truncated;
-  double* end_obs;          // [.][obs_dim]
-  float* end_mean;          // [.][A] the policy's mean at s_T of a cut-off path, zeros otherwise
-  int64_t* end_len;
-  int64_t* end_row;
-};
-struct GaussRolloutOut {    // concatenated outputs; any pointer may be NULL
-  double* obs64;            // [N][obs_dim]
-  double* env_state;        // [N][state_dim]
-  float* X;                 // [N][ldx]
-  int ldx;
-  float* actions;           // [N][ld_act]
-  int ld_act;
-  float* means;             // [N][ld_mean]
-  int ld_mean;
-  double* normals;          // [N][A]
-  double* rewards;
-  uint8_t* starts;
-  const int64_t* path_offsets;   // as RolloutOut: the end records are written when given
-  int ends_only;
-  uint8_t* end_truncated;
-  double* end_obs64;        // [n_paths][obs_dim]
-  float* end_obs32;
-  float* end_mean;          // [n_paths][A]
-  int64_t* end_len;
-  int64_t* end_rows;
-};
-void launch_rollout_gaussian(const GaussRolloutArgs& a, hipStream_t s);
-void launch_rollout_gaussian_compact(const GaussRolloutArgs& a, const int64_t* offsets, const GaussRolloutOut& o,
-                                     int64_t max_count, hipStream_t s);
-// state [n][state_dim], action [n][act_dim] f32 -> state_out, obs_out [n][obs_dim], reward, done; outputs may be NULL
-void launch_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
-                          double* obs_out, double* reward, uint8_t* done, hipStream_t s);
 }  // namespace trpo
 
 namespace trpo {

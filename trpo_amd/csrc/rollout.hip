@@ -17,10 +17,14 @@
 //     restated the same way (include/trpo_engine.h spells out their equations).  The rollout is one
 //     kernel over an environment trait (reset, step, observe and the dimensions), so that a task whose
 //     state is not its observation (Acrobot) or whose reward is not constant costs no second kernel.
-//   * Pendulum-v1 and MountainCarContinuous-v0 under the diagonal-Gaussian policy: the same rollout over a
-//     continuous-action trait, which steps with the float32 action components, sampled as act_gaussian does
+//   * Pendulum-v1 and MountainCarContinuous-v0 under the diagonal-Gaussian policy: the same kernel over a trait
+//     with kContinuous set, which steps with the float32 action components, sampled as act_gaussian does
 //     (gauss_act) from Box-Muller normals off the same Philox stream; it records action, mean and normal per
 //     component, and samples with the copy of the log-std vector the engine took when the rollout began.
+//
+// What depends on the policy head sits behind `if constexpr (Env::kContinuous)`: the forward (softmax or mean),
+// the sample, the per-step records of head row, action and draw, and the trait's step().  The head row -- the
+// distribution or the mean, kHead floats -- is rerun at s_T and compacted by the same lines for both.
 //
 // One wave simulates one environment for its whole share of the rollout: the
 // policy forward is wave-parallel over output units (activations in a per-wave
@@ -38,7 +42,7 @@
 // did not terminate the environment, the time limit or max_pathlength ended it --
 // or terminated (a step that does both is a termination), the state s_T after the
 // last step, T, the path's last row and, for a cut-off path, the policy's
-// distribution at s_T from one more forward that draws no uniform.  The
+// distribution (or mean) at s_T from one more forward that draws nothing.  The
 // compaction kernel concatenates these records too, so that GAE can bootstrap the
 // cut-off paths from V(s_T) (vf.hip: the VF's features are [obs | dist | t/10]).
 // The per-step outputs and the Philox draw indices do not depend on any of it.
@@ -116,10 +120,11 @@ __device__ __forceinline__ bool cartpole_step(double (&s)[4], int action) {
 }
 
 // The rollout's view of an environment.  kObsIsState: the observation is the state itself, so the per-step
-// record of the state is the record of the observation and no second array is written.
+// record of the state is the record of the observation and no second array is written.  kHead: the width of the
+// policy's output row, the number of actions or (kContinuous) of float32 action components step() takes.
 struct CartPoleV0 {
-  static constexpr int kState = 4, kObs = 4, kActions = 2, kResetDraws = 4, kTimeLimit = 200;
-  static constexpr bool kObsIsState = true;
+  static constexpr int kState = 4, kObs = 4, kHead = 2, kResetDraws = 4, kTimeLimit = 200;
+  static constexpr bool kObsIsState = true, kContinuous = false;
   static constexpr const char* kName = "CartPole-v0";
   // env.reset(): np_random.uniform(-0.05, 0.05, size=(4,))
   static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
@@ -140,8 +145,8 @@ __device__ __forceinline__ double clampd(double x, double lo, double hi) {   // 
 
 // ---- MountainCar-v0 (gym classic_control/mountain_car.py), float64 -----------------------------------
 struct MountainCarV0 {
-  static constexpr int kState = 2, kObs = 2, kActions = 3, kResetDraws = 1, kTimeLimit = 200;
-  static constexpr bool kObsIsState = true;
+  static constexpr int kState = 2, kObs = 2, kHead = 3, kResetDraws = 1, kTimeLimit = 200;
+  static constexpr bool kObsIsState = true, kContinuous = false;
   static constexpr const char* kName = "MountainCar-v0";
   static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
     s[0] = -0.6 + (-0.4 - -0.6) * u[0];
@@ -164,8 +169,8 @@ struct MountainCarV0 {
 
 // ---- Acrobot-v1 (gym classic_control/acrobot.py, "book" dynamics, one RK4 step), float64 -------------
 struct AcrobotV1 {
-  static constexpr int kState = 4, kObs = 6, kActions = 3, kResetDraws = 4, kTimeLimit = 500;
-  static constexpr bool kObsIsState = false;
+  static constexpr int kState = 4, kObs = 6, kHead = 3, kResetDraws = 4, kTimeLimit = 500;
+  static constexpr bool kObsIsState = false, kContinuous = false;
   static constexpr const char* kName = "Acrobot-v1";
   static constexpr double kPi = 3.141592653589793;
   static constexpr double m1 = 1.0, m2 = 1.0, l1 = 1.0, lc1 = 0.5, lc2 = 0.5, I1 = 1.0, I2 = 1.0, g = 9.8, dt = 0.2;
@@ -242,19 +247,19 @@ bool with_env(int env, F&& f) {
 }
 
 // ---- the continuous-action environments (TRPO_CENV_*; include/trpo_engine.h spells out their equations) ----
-// A trait of this kind steps with the kActDim float32 action components the policy produced, widened to float64.
+// A trait of this kind steps with the kHead float32 action components the policy produced, widened to float64.
 
 // Pendulum-v1 (gym classic_control/pendulum.py), float64
 struct PendulumV1 {
-  static constexpr int kState = 2, kObs = 3, kActDim = 1, kResetDraws = 2, kTimeLimit = 200;
-  static constexpr bool kObsIsState = false;
+  static constexpr int kState = 2, kObs = 3, kHead = 1, kResetDraws = 2, kTimeLimit = 200;
+  static constexpr bool kObsIsState = false, kContinuous = true;
   static constexpr const char* kName = "Pendulum-v1";
   static constexpr double kPi = 3.141592653589793;
   static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
     s[0] = -kPi + (kPi - -kPi) * u[0];
     s[1] = -1.0 + (1.0 - -1.0) * u[1];
   }
-  static __device__ __forceinline__ bool step(double (&s)[kState], const float (&act)[kActDim], double& reward) {
+  static __device__ __forceinline__ bool step(double (&s)[kState], const float (&act)[kHead], double& reward) {
     const double th = s[0], thd = s[1];
     const double u = clampd((double)act[0], -2.0, 2.0);
     const double y = th + kPi;
@@ -277,14 +282,14 @@ struct PendulumV1 {
 
 // MountainCarContinuous-v0 (gym classic_control/continuous_mountain_car.py), float64
 struct MountainCarContinuousV0 {
-  static constexpr int kState = 2, kObs = 2, kActDim = 1, kResetDraws = 1, kTimeLimit = 999;
-  static constexpr bool kObsIsState = true;
+  static constexpr int kState = 2, kObs = 2, kHead = 1, kResetDraws = 1, kTimeLimit = 999;
+  static constexpr bool kObsIsState = true, kContinuous = true;
   static constexpr const char* kName = "MountainCarContinuous-v0";
   static __device__ __forceinline__ void reset(double (&s)[kState], const double* u) {
     s[0] = -0.6 + (-0.4 - -0.6) * u[0];
     s[1] = 0.0;
   }
-  static __device__ __forceinline__ bool step(double (&s)[kState], const float (&act)[kActDim], double& reward) {
+  static __device__ __forceinline__ bool step(double (&s)[kState], const float (&act)[kHead], double& reward) {
     const double a = (double)act[0];
     double p = s[0], v = s[1];
     const double f = clampd(a, -1.0, 1.0);
@@ -311,6 +316,11 @@ bool with_cenv(int cenv, F&& f) {
     default: return false;
   }
 }
+// either id table, by the policy head the environment is rolled out under
+template <class F>
+bool with_any_env(bool continuous, int env, F&& f) {
+  return continuous ? with_cenv(env, f) : with_env(env, f);
+}
 
 // ---- wave-level policy forward ---------------------------------------------------------------
 __device__ __forceinline__ void wave_sync() {
@@ -326,6 +336,10 @@ __device__ __forceinline__ float wave_sumf(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
+}
+// lane src's v in every lane; src must be the same in all lanes
+__device__ __forceinline__ float wave_bcast(float v, int src) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
 // h_{l} = tanh(h_{l-1} W_l + b_l), the last layer linear (trpo_inksci.py:38-39); `in` holds the obs (w[0]
@@ -365,7 +379,7 @@ __device__ float wave_policy(const PolicyShape& ps, const float* theta, float* i
 
 // cat_sample (utils.py:95-105) on the wave's distribution: csprob = float32 cumsum, first k with
 // csprob > r (float64 comparison), 0 if none.  train = 0: argmax (trpo_inksci.py:82), first max.
-__device__ __forceinline__ int wave_choose(float p, int A, double r, int train, int lane) {
+__device__ __forceinline__ int wave_choose(float p, int A, double r, int train) {
   int out = 0;
   if (train) {
     float cs = 0.0f;
@@ -386,7 +400,6 @@ __device__ __forceinline__ int wave_choose(float p, int A, double r, int train, 
       }
     }
   }
-  (void)lane;
   return out;
 }
 
@@ -398,12 +411,28 @@ __device__ __forceinline__ float gauss_act(float mu, float logstd, double xi) {
   return (float)((double)mu + noise);
 }
 
+// this lane's entry of the policy's head row at the obs in `in` (lanes >= A: 0): its softmax probability, or
+// (kContinuous) its component of the mean.  All lanes must call.
+template <bool kContinuous>
+__device__ __forceinline__ float wave_head(const PolicyShape& ps, const float* theta, float* in, float* out, int A,
+                                           int lane) {
+  if constexpr (kContinuous) {
+    const float* mu = wave_layers(ps, theta, in, out, lane);
+    return lane < A ? mu[lane] : 0.0f;
+  } else {
+    return wave_policy(ps, theta, in, out, lane);
+  }
+}
+
 constexpr int kRollWaves = 4;
 
+// The draw of an environment's step k (counted over all its episodes) is Philox (seed, env, stream 0, .): the
+// uniform at k, or (kContinuous) the normal of component d at k * A + d, whether or not train.
 template <class Env>
 __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutArgs a) {
   extern __shared__ float lds[];
-  constexpr int kS = Env::kState, obs_dim = Env::kObs, A = Env::kActions;   // the engine checked ps against them
+  constexpr int kS = Env::kState, obs_dim = Env::kObs, A = Env::kHead;   // the engine checked ps against them
+  constexpr bool kCont = Env::kContinuous;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int env = blockIdx.x * kRollWaves + wv;
   if (env >= a.n_envs) return;
@@ -412,7 +441,6 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
   const int64_t base = (int64_t)env * a.env_cap;
   int64_t count = 0;
   int episode = 0;
-  uint64_t adraw = 0;
   while (count < a.budget) {
     // env.reset() from kResetDraws uniforms
     double u[Env::kResetDraws];
@@ -437,18 +465,40 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
         if (lane < kS) a.env_state[row * kS + lane] = s[lane];
       }
       wave_sync();
-      const float p = wave_policy(a.ps, a.theta, buf0, buf1, lane);
-      const double r = a.act_u ? a.act_u[row] : uniform53(a.seed, (uint32_t)env, 0u, adraw);
-      ++adraw;
-      const int action = wave_choose(p, A, r, a.train, lane);
-      if (lane < A) a.dist[row * A + lane] = p;
+      const float h = wave_head<kCont>(a.ps, a.theta, buf0, buf1, A, lane);
+      // Where the stores sit matters to the step's latency: the compiler reloads their pointers from the kernel
+      // arguments inside this loop, one wait per group of stores.
       double reward;
-      done = Env::step(s, action, reward);
+      if constexpr (kCont) {
+        // every lane forms the whole action, as it holds the whole state; lane d records component d
+        float act[A];
+#pragma unroll
+        for (int d = 0; d < A; ++d) {
+          const float m = wave_bcast(h, d);
+          double xi = 0.0;
+          if (a.train)
+            xi = a.draws ? a.draws[row * A + d] : normal53(a.seed, (uint32_t)env, 0u, (uint64_t)count * A + d);
+          act[d] = a.train ? gauss_act(m, a.logstd[d], xi) : m;
+          if (lane == d) {
+            a.actf[row * A + d] = act[d];
+            a.head[row * A + d] = m;
+            a.noise[row * A + d] = xi;
+          }
+        }
+        done = Env::step(s, act, reward);
+      } else {
+        if (lane < A) a.head[row * A + lane] = h;
+        const double r = a.draws ? a.draws[row] : uniform53(a.seed, (uint32_t)env, 0u, (uint64_t)count);
+        const int action = wave_choose(h, A, r, a.train);
+        done = Env::step(s, action, reward);
+        if (lane == 0) {
+          a.acti[row] = action;
+          a.noise[row] = r;
+        }
+      }
       if (lane == 0) {
-        a.actions[row] = action;
         a.rewards[row] = reward;
         a.starts[row] = t == 0 ? 1 : 0;
-        if (a.uniforms_out) a.uniforms_out[row] = r;
       }
       ++count;
       len = t + 1;
@@ -459,20 +509,20 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
     wave_sync();
     // How the path ended.  It was cut off (truncated) when its last step did not terminate the environment:
     // the time limit or max_pathlength ended it, and a step that does both counts as terminated.  s is s_T;
-    // its observation is recorded, and a cut-off path also records the policy's distribution there, the VF's
-    // features of s_T (vf.hip).  The extra forward draws no uniform.
+    // its observation is recorded, and a cut-off path also records the policy's head row there (the distribution
+    // is among the VF's features of s_T, vf.hip).  The extra forward draws nothing.
     const int64_t path = (int64_t)env * a.budget + (episode - 1);
     const bool truncated = !done;
     const double obT = lane < obs_dim ? Env::observe(s, lane) : 0.0;
-    float pT = 0.0f;
+    float hT = 0.0f;
     if (truncated) {
       if (lane < obs_dim) buf0[lane] = (float)obT;
       wave_sync();
-      pT = wave_policy(a.ps, a.theta, buf0, buf1, lane);
+      hT = wave_head<kCont>(a.ps, a.theta, buf0, buf1, A, lane);
       wave_sync();
     }
     if (lane < obs_dim) a.end_obs[path * obs_dim + lane] = obT;
-    if (lane < A) a.end_dist[path * A + lane] = pT;
+    if (lane < A) a.end_head[path * A + lane] = hT;
     if (lane == 0) {
       a.end_truncated[path] = truncated ? 1 : 0;
       a.end_len[path] = len;
@@ -499,15 +549,15 @@ __global__ void __launch_bounds__(256) rollout_compact_kernel(const RolloutArgs 
       if (o.X) o.X[d * o.ldx + c] = (float)v;
     }
     for (int c = 0; c < A; ++c) {
-      const float v = a.dist[s * A + c];
-      if (o.dist) o.dist[d * A + c] = v;
-      if (o.old) o.old[d * o.ld_old + c] = v;
+      if (o.head) o.head[d * o.ld_head + c] = a.head[s * A + c];
+      if (o.actf) o.actf[d * o.ld_actf + c] = a.actf[s * A + c];
     }
-    if (o.actions64) o.actions64[d] = a.actions[s];
-    if (o.act32) o.act32[d] = a.actions[s];
+    if (o.actions64) o.actions64[d] = a.acti[s];
+    if (o.act32) o.act32[d] = a.acti[s];
+    if (o.noise)
+      for (int c = 0; c < a.noise_dim; ++c) o.noise[d * a.noise_dim + c] = a.noise[s * a.noise_dim + c];
     if (o.rewards) o.rewards[d] = a.rewards[s];
     if (o.starts) o.starts[d] = a.starts[s];
-    if (o.uniforms && a.uniforms_out) o.uniforms[d] = a.uniforms_out[s];
     if (o.env_state) {   // an environment whose observation is its state recorded it once, as obs
       const double* st = a.env_state ? a.env_state : a.obs;
       for (int c = 0; c < a.state_dim; ++c) o.env_state[d * a.state_dim + c] = st[s * a.state_dim + c];
@@ -523,8 +573,8 @@ __global__ void __launch_bounds__(256) rollout_compact_kernel(const RolloutArgs 
       if (o.end_obs64) o.end_obs64[d * obs_dim + c] = v;
       if (o.end_obs32) o.end_obs32[d * obs_dim + c] = (float)v;
     }
-    if (o.end_dist)
-      for (int c = 0; c < A; ++c) o.end_dist[d * A + c] = a.end_dist[s * A + c];
+    if (o.end_head)
+      for (int c = 0; c < A; ++c) o.end_head[d * A + c] = a.end_head[s * A + c];
     if (o.end_truncated) o.end_truncated[d] = a.end_truncated[s];
     if (o.end_len) o.end_len[d] = a.end_len[s];
     if (o.end_rows) o.end_rows[d] = dst0 + a.end_row[s];
@@ -545,7 +595,7 @@ __global__ void __launch_bounds__(kRollWaves * 64) act_kernel(const PolicyShape 
   for (int c = lane; c < obs_dim; c += 64) buf0[c] = states[row * obs_dim + c];
   wave_sync();
   const float p = wave_policy(ps, theta, buf0, buf1, lane);
-  const int action = wave_choose(p, A, r ? r[row] : 0.0, train, lane);
+  const int action = wave_choose(p, A, r ? r[row] : 0.0, train);
   if (lane < A && dists) dists[row * A + lane] = p;
   if (lane == 0 && actions) actions[row] = action;
 }
@@ -574,139 +624,6 @@ __global__ void __launch_bounds__(kRollWaves * 64) act_gaussian_kernel(const Pol
   }
 }
 
-// The rollout under the diagonal-Gaussian policy: rollout_kernel with the mean forward and gauss_act in place of
-// softmax + cat_sample, over a continuous-action environment trait.  The normal of component d at an environment's
-// step k (counted over all its episodes, whether or not train) is Philox (seed, env, stream 0, k * A + d).
-template <class Env>
-__global__ void __launch_bounds__(kRollWaves * 64) rollout_gaussian_kernel(const GaussRolloutArgs a) {
-  extern __shared__ float lds[];
-  constexpr int kS = Env::kState, obs_dim = Env::kObs, A = Env::kActDim;   // the engine checked ps against them
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int env = blockIdx.x * kRollWaves + wv;
-  if (env >= a.n_envs) return;
-  float* buf0 = lds + (size_t)wv * 2 * a.maxw;
-  float* buf1 = buf0 + a.maxw;
-  const int64_t base = (int64_t)env * a.env_cap;
-  int64_t count = 0;
-  int episode = 0;
-  while (count < a.budget) {
-    double u[Env::kResetDraws];
-#pragma unroll
-    for (int i = 0; i < Env::kResetDraws; ++i)
-      u[i] = a.reset_u ? a.reset_u[((int64_t)env * a.max_episodes + episode) * Env::kResetDraws + i]
-                       : uniform53(a.seed, (uint32_t)env, 1u, (uint64_t)episode * Env::kResetDraws + i);
-    double s[kS];
-    Env::reset(s, u);
-    ++episode;
-    bool done = false;
-    int len = 0;
-    for (int t = 0; t < a.max_pathlength; ++t) {
-      const int64_t row = base + count;
-      if (lane < obs_dim) {
-        const double ob = Env::observe(s, lane);
-        buf0[lane] = (float)ob;
-        a.obs[row * obs_dim + lane] = ob;
-      }
-      if constexpr (!Env::kObsIsState) {
-        if (lane < kS) a.env_state[row * kS + lane] = s[lane];
-      }
-      wave_sync();
-      const float* mu = wave_layers(a.ps, a.theta, buf0, buf1, lane);
-      // every lane forms the whole action, as it holds the whole state; lane d records component d
-      float act[A];
-#pragma unroll
-      for (int d = 0; d < A; ++d) {
-        const float m = mu[d];
-        double xi = 0.0;
-        if (a.train)
-          xi = a.act_n ? a.act_n[row * A + d] : normal53(a.seed, (uint32_t)env, 0u, (uint64_t)count * A + d);
-        act[d] = a.train ? gauss_act(m, a.logstd[d], xi) : m;
-        if (lane == d) {
-          a.actions[row * A + d] = act[d];
-          a.means[row * A + d] = m;
-          a.normals[row * A + d] = xi;
-        }
-      }
-      double reward;
-      done = Env::step(s, act, reward);
-      if (lane == 0) {
-        a.rewards[row] = reward;
-        a.starts[row] = t == 0 ? 1 : 0;
-      }
-      ++count;
-      len = t + 1;
-      if (done || t + 1 >= a.time_limit) break;
-      wave_sync();
-    }
-    wave_sync();
-    // how the path ended, as rollout_kernel records it; a cut-off path records the policy's mean at s_T
-    const int64_t path = (int64_t)env * a.budget + (episode - 1);
-    const bool truncated = !done;
-    const double obT = lane < obs_dim ? Env::observe(s, lane) : 0.0;
-    float muT = 0.0f;
-    if (truncated) {
-      if (lane < obs_dim) buf0[lane] = (float)obT;
-      wave_sync();
-      const float* mu = wave_layers(a.ps, a.theta, buf0, buf1, lane);
-      if (lane < A) muT = mu[lane];
-      wave_sync();
-    }
-    if (lane < obs_dim) a.end_obs[path * obs_dim + lane] = obT;
-    if (lane < A) a.end_mean[path * A + lane] = muT;
-    if (lane == 0) {
-      a.end_truncated[path] = truncated ? 1 : 0;
-      a.end_len[path] = len;
-      a.end_row[path] = count - 1;
-    }
-  }
-  if (lane == 0) {
-    a.counts[env] = count;
-    a.episodes[env] = episode;
-  }
-}
-
-// concatenate the per-environment regions of a Gaussian rollout in environment order
-__global__ void __launch_bounds__(256) rollout_gaussian_compact_kernel(const GaussRolloutArgs a,
-                                                                       const int64_t* offsets, GaussRolloutOut o) {
-  const int obs_dim = a.ps.w[0], A = a.ps.w[a.ps.L];
-  const int env = blockIdx.y;
-  const int64_t cnt = o.ends_only ? 0 : a.counts[env], dst0 = offsets[env], src0 = (int64_t)env * a.env_cap;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t s = src0 + i, d = dst0 + i;
-    for (int c = 0; c < obs_dim; ++c) {
-      const double v = a.obs[s * obs_dim + c];
-      if (o.obs64) o.obs64[d * obs_dim + c] = v;
-      if (o.X) o.X[d * o.ldx + c] = (float)v;
-    }
-    for (int c = 0; c < A; ++c) {
-      if (o.actions) o.actions[d * o.ld_act + c] = a.actions[s * A + c];
-      if (o.means) o.means[d * o.ld_mean + c] = a.means[s * A + c];
-      if (o.normals) o.normals[d * A + c] = a.normals[s * A + c];
-    }
-    if (o.rewards) o.rewards[d] = a.rewards[s];
-    if (o.starts) o.starts[d] = a.starts[s];
-    if (o.env_state) {   // an environment whose observation is its state recorded it once, as obs
-      const double* st = a.env_state ? a.env_state : a.obs;
-      for (int c = 0; c < a.state_dim; ++c) o.env_state[d * a.state_dim + c] = st[s * a.state_dim + c];
-    }
-  }
-  if (!o.path_offsets) return;
-  const int64_t np = a.episodes[env], pdst0 = o.path_offsets[env], psrc0 = (int64_t)env * a.budget;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t s = psrc0 + i, d = pdst0 + i;
-    for (int c = 0; c < obs_dim; ++c) {
-      const double v = a.end_obs[s * obs_dim + c];
-      if (o.end_obs64) o.end_obs64[d * obs_dim + c] = v;
-      if (o.end_obs32) o.end_obs32[d * obs_dim + c] = (float)v;
-    }
-    if (o.end_mean)
-      for (int c = 0; c < A; ++c) o.end_mean[d * A + c] = a.end_mean[s * A + c];
-    if (o.end_truncated) o.end_truncated[d] = a.end_truncated[s];
-    if (o.end_len) o.end_len[d] = a.end_len[s];
-    if (o.end_rows) o.end_rows[d] = dst0 + a.end_row[s];
-  }
-}
-
 __global__ void __launch_bounds__(256) cat_sample_kernel(const float* prob, int64_t n, int k, const double* r,
                                                          int64_t* out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -723,58 +640,27 @@ __global__ void __launch_bounds__(256) cat_sample_kernel(const float* prob, int6
   }
 }
 
-__global__ void __launch_bounds__(256) cartpole_step_kernel(const double* state, const int64_t* action, int64_t n,
-                                                            double* state_out, double* reward, uint8_t* done) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    double s[4] = {state[4 * i], state[4 * i + 1], state[4 * i + 2], state[4 * i + 3]};
-    const bool d = cartpole_step(s, (int)action[i]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) state_out[4 * i + j] = s[j];
-    if (reward) reward[i] = 1.0;
-    if (done) done[i] = d ? 1 : 0;
-  }
-}
-
-// one step per row of any environment: the state after it, its observation, reward and termination
+// one step per row of any environment: the state after it, its observation, reward and termination; action is
+// [n] i64, or (kContinuous) [n][kHead] f32
 template <class Env>
-__global__ void __launch_bounds__(256) env_step_kernel(const double* state, const int64_t* action, int64_t n,
+__global__ void __launch_bounds__(256) env_step_kernel(const double* state, const void* action, int64_t n,
                                                        double* state_out, double* obs_out, double* reward,
                                                        uint8_t* done) {
-  constexpr int kS = Env::kState, kO = Env::kObs;
+  constexpr int kS = Env::kState, kO = Env::kObs, kA = Env::kHead;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     double s[kS];
 #pragma unroll
     for (int j = 0; j < kS; ++j) s[j] = state[kS * i + j];
     double rw;
-    const bool d = Env::step(s, (int)action[i], rw);
-    if (state_out) {
+    bool d;
+    if constexpr (Env::kContinuous) {
+      float act[kA];
 #pragma unroll
-      for (int j = 0; j < kS; ++j) state_out[kS * i + j] = s[j];
+      for (int j = 0; j < kA; ++j) act[j] = static_cast<const float*>(action)[kA * i + j];
+      d = Env::step(s, act, rw);
+    } else {
+      d = Env::step(s, (int)static_cast<const int64_t*>(action)[i], rw);
     }
-    if (obs_out) {
-#pragma unroll
-      for (int j = 0; j < kO; ++j) obs_out[kO * i + j] = Env::observe(s, j);
-    }
-    if (reward) reward[i] = rw;
-    if (done) done[i] = d ? 1 : 0;
-  }
-}
-
-// ... and of a continuous-action environment: action [n][kActDim] f32
-template <class Env>
-__global__ void __launch_bounds__(256) cont_env_step_kernel(const double* state, const float* action, int64_t n,
-                                                            double* state_out, double* obs_out, double* reward,
-                                                            uint8_t* done) {
-  constexpr int kS = Env::kState, kO = Env::kObs, kA = Env::kActDim;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    double s[kS];
-#pragma unroll
-    for (int j = 0; j < kS; ++j) s[j] = state[kS * i + j];
-    float act[kA];
-#pragma unroll
-    for (int j = 0; j < kA; ++j) act[j] = action[kA * i + j];
-    double rw;
-    const bool d = Env::step(s, act, rw);
     if (state_out) {
 #pragma unroll
       for (int j = 0; j < kS; ++j) state_out[kS * i + j] = s[j];
@@ -797,16 +683,16 @@ inline unsigned grid1(int64_t n) {
 
 size_t rollout_lds_bytes(int maxw) { return (size_t)kRollWaves * 2 * maxw * sizeof(float); }
 
-bool env_dims(int env, EnvDims* out) {
-  return with_env(env, [&](auto e) {
+bool env_dims(bool continuous, int env, EnvDims* out) {
+  return with_any_env(continuous, env, [&](auto e) {
     using Env = decltype(e);
-    *out = EnvDims{Env::kObs, Env::kState, Env::kActions, Env::kResetDraws, Env::kTimeLimit, Env::kName};
+    *out = EnvDims{Env::kObs, Env::kState, Env::kHead, Env::kResetDraws, Env::kTimeLimit, Env::kName};
   });
 }
 
 void launch_rollout(const RolloutArgs& a, hipStream_t s) {
   const unsigned blocks = (unsigned)((a.n_envs + kRollWaves - 1) / kRollWaves);
-  const bool known = with_env(a.env, [&](auto e) {
+  const bool known = with_any_env(a.continuous, a.env, [&](auto e) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(rollout_kernel<decltype(e)>), dim3(blocks), dim3(kRollWaves * 64),
                        rollout_lds_bytes(a.maxw), s, a);
   });
@@ -840,52 +726,14 @@ void launch_cat_sample(const float* prob, int64_t n, int k, const double* r, int
   hipLaunchKernelGGL(cat_sample_kernel, dim3(grid1(n)), dim3(256), 0, s, prob, n, k, r, out);
 }
 
-void launch_cartpole_step(const double* state, const int64_t* action, int64_t n, double* state_out, double* reward,
-                          uint8_t* done, hipStream_t s) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(cartpole_step_kernel, dim3(grid1(n)), dim3(256), 0, s, state, action, n, state_out, reward, done);
-}
-
-void launch_env_step(int env, const double* state, const int64_t* action, int64_t n, double* state_out,
+void launch_env_step(bool continuous, int env, const double* state, const void* action, int64_t n, double* state_out,
                      double* obs_out, double* reward, uint8_t* done, hipStream_t s) {
-  const bool known = with_env(env, [&](auto e) {
+  const bool known = with_any_env(continuous, env, [&](auto e) {
     if (n <= 0) return;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(env_step_kernel<decltype(e)>), dim3(grid1(n)), dim3(256), 0, s, state, action,
                        n, state_out, obs_out, reward, done);
   });
   if (!known) throw std::invalid_argument("launch_env_step: unknown environment id");
-}
-
-bool cont_env_dims(int cenv, ContEnvDims* out) {
-  return with_cenv(cenv, [&](auto e) {
-    using Env = decltype(e);
-    *out = ContEnvDims{Env::kObs, Env::kState, Env::kActDim, Env::kResetDraws, Env::kTimeLimit, Env::kName};
-  });
-}
-
-void launch_rollout_gaussian(const GaussRolloutArgs& a, hipStream_t s) {
-  const unsigned blocks = (unsigned)((a.n_envs + kRollWaves - 1) / kRollWaves);
-  const bool known = with_cenv(a.cenv, [&](auto e) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(rollout_gaussian_kernel<decltype(e)>), dim3(blocks), dim3(kRollWaves * 64),
-                       rollout_lds_bytes(a.maxw), s, a);
-  });
-  if (!known) throw std::invalid_argument("launch_rollout_gaussian: unknown continuous environment id");
-}
-
-void launch_rollout_gaussian_compact(const GaussRolloutArgs& a, const int64_t* offsets, const GaussRolloutOut& o,
-                                     int64_t max_count, hipStream_t s) {
-  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_count + 255) / 256, 64));
-  hipLaunchKernelGGL(rollout_gaussian_compact_kernel, dim3(bx, a.n_envs), dim3(256), 0, s, a, offsets, o);
-}
-
-void launch_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
-                          double* obs_out, double* reward, uint8_t* done, hipStream_t s) {
-  const bool known = with_cenv(cenv, [&](auto e) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(cont_env_step_kernel<decltype(e)>), dim3(grid1(n)), dim3(256), 0, s, state,
-                       action, n, state_out, obs_out, reward, done);
-  });
-  if (!known) throw std::invalid_argument("launch_cont_env_step: unknown continuous environment id");
 }
 
 }  // namespace trpo

@@ -41,11 +41,11 @@ int trpo_env_info(int env, trpo_env_info_t* out) {
   return guarded([&] {
     REQUIRE(out, "NULL argument");
     EnvDims d{};
-    REQUIRE(env_dims(env, &d), "unknown environment id " + std::to_string(env));
+    REQUIRE(env_dims(false, env, &d), "unknown environment id " + std::to_string(env));
     std::memset(out, 0, sizeof *out);
     out->obs_dim = d.obs_dim;
     out->state_dim = d.state_dim;
-    out->n_actions = d.n_actions;
+    out->n_actions = d.head_dim;
     out->reset_draws = d.reset_draws;
     out->time_limit = d.time_limit;
     std::strncpy(out->name, d.name, sizeof out->name - 1);
@@ -56,7 +56,7 @@ int trpo_default_rollout_params_env(int env, trpo_rollout_params* p) {
   return guarded([&] {
     REQUIRE(p, "NULL argument");
     EnvDims d{};
-    REQUIRE(env_dims(env, &d), "unknown environment id " + std::to_string(env));
+    REQUIRE(env_dims(false, env, &d), "unknown environment id " + std::to_string(env));
     trpo_default_rollout_params(p);
     p->time_limit = d.time_limit;
   });
@@ -66,7 +66,7 @@ int trpo_env_step(int env, const double* state, const int64_t* action, int64_t n
                   double* reward, uint8_t* done, int mem) {
   return guarded([&] {
     EnvDims d{};
-    REQUIRE(env_dims(env, &d), "unknown environment id " + std::to_string(env));
+    REQUIRE(env_dims(false, env, &d), "unknown environment id " + std::to_string(env));
     REQUIRE(state && action && n >= 0, "bad argument");
     if (n == 0) return;
     Staging st(mem, nullptr);
@@ -75,7 +75,7 @@ int trpo_env_step(int env, const double* state, const int64_t* action, int64_t n
     double* dso = st.out(state_out, (size_t)n * d.state_dim);
     double* dob = st.out(obs_out, (size_t)n * d.obs_dim);
     double* dr = st.out(reward, (size_t)n);
-    launch_env_step(env, ds, da, n, dso, dob, dr, st.out(done, (size_t)n), nullptr);
+    launch_env_step(false, env, ds, da, n, dso, dob, dr, st.out(done, (size_t)n), nullptr);
     check_launch();
     st.fetch();
     HIPCHECK(hipDeviceSynchronize());
@@ -85,12 +85,12 @@ int trpo_env_step(int env, const double* state, const int64_t* action, int64_t n
 int trpo_cont_env_info(int cenv, trpo_cont_env_info_t* out) {
   return guarded([&] {
     REQUIRE(out, "NULL argument");
-    ContEnvDims d{};
-    REQUIRE(cont_env_dims(cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
+    EnvDims d{};
+    REQUIRE(env_dims(true, cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
     std::memset(out, 0, sizeof *out);
     out->obs_dim = d.obs_dim;
     out->state_dim = d.state_dim;
-    out->act_dim = d.act_dim;
+    out->act_dim = d.head_dim;
     out->reset_draws = d.reset_draws;
     out->time_limit = d.time_limit;
     std::strncpy(out->name, d.name, sizeof out->name - 1);
@@ -100,8 +100,8 @@ int trpo_cont_env_info(int cenv, trpo_cont_env_info_t* out) {
 int trpo_default_rollout_params_cont(int cenv, trpo_rollout_params* p) {
   return guarded([&] {
     REQUIRE(p, "NULL argument");
-    ContEnvDims d{};
-    REQUIRE(cont_env_dims(cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
+    EnvDims d{};
+    REQUIRE(env_dims(true, cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
     trpo_default_rollout_params(p);
     p->time_limit = d.time_limit;
   });
@@ -110,17 +110,17 @@ int trpo_default_rollout_params_cont(int cenv, trpo_rollout_params* p) {
 int trpo_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
                        double* obs_out, double* reward, uint8_t* done, int mem) {
   return guarded([&] {
-    ContEnvDims d{};
-    REQUIRE(cont_env_dims(cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
+    EnvDims d{};
+    REQUIRE(env_dims(true, cenv, &d), "unknown continuous environment id " + std::to_string(cenv));
     REQUIRE(state && action && n >= 0, "bad argument");
     if (n == 0) return;
     Staging st(mem, nullptr);
     const double* ds = st.in(state, (size_t)n * d.state_dim);
-    const float* da = st.in(action, (size_t)n * d.act_dim);
+    const float* da = st.in(action, (size_t)n * d.head_dim);
     double* dso = st.out(state_out, (size_t)n * d.state_dim);
     double* dob = st.out(obs_out, (size_t)n * d.obs_dim);
     double* dr = st.out(reward, (size_t)n);
-    launch_cont_env_step(cenv, ds, da, n, dso, dob, dr, st.out(done, (size_t)n), nullptr);
+    launch_env_step(true, cenv, ds, da, n, dso, dob, dr, st.out(done, (size_t)n), nullptr);
     check_launch();
     st.fetch();
     HIPCHECK(hipDeviceSynchronize());
@@ -161,7 +161,7 @@ int trpo_cartpole_step(const double* state, const int64_t* action, int64_t n, do
     const int64_t* da = st.in(action, (size_t)n);
     double* dso = st.out(state_out, (size_t)n * 4);
     double* dr = st.out(reward, (size_t)n);
-    launch_cartpole_step(ds, da, n, dso, dr, st.out(done, (size_t)n), nullptr);
+    launch_env_step(false, TRPO_ENV_CARTPOLE_V0, ds, da, n, dso, nullptr, dr, st.out(done, (size_t)n), nullptr);
     check_launch();
     st.fetch();
     HIPCHECK(hipDeviceSynchronize());

@@ -459,8 +459,9 @@ class Engine:
         instances on the GPU.  Returns (total steps, number of paths)."""
         p = _lib.RolloutParams()
         lib.trpo_default_rollout_params(ctypes.byref(p))
-        return self._rollout(None, p, n_envs, n_timesteps, max_pathlength, seed, train, time_limit,
-                             reset_uniforms, action_uniforms, max_episodes_per_env)
+        return self._rollout("trpo_rollout_cartpole", (), env_info, _lib.ENV_CARTPOLE_V0, p, n_envs, n_timesteps,
+                             max_pathlength, seed, train, time_limit, reset_uniforms, action_uniforms,
+                             max_episodes_per_env)
 
     def rollout(self, env="CartPole-v0", n_envs: int = 1, n_timesteps: int = 1000, max_pathlength: int = 1000,
                 seed: int = 1, train: bool = True, time_limit: Optional[int] = None,
@@ -471,14 +472,17 @@ class Engine:
         eid = _env_id(env)
         p = _lib.RolloutParams()
         check(lib.trpo_default_rollout_params_env(eid, ctypes.byref(p)), "trpo_default_rollout_params_env")
-        return self._rollout(eid, p, n_envs, n_timesteps, max_pathlength, seed, train,
-                             p.time_limit if time_limit is None else time_limit,
-                             reset_uniforms, action_uniforms, max_episodes_per_env)
+        return self._rollout("trpo_rollout_env", (eid,), env_info, eid, p, n_envs, n_timesteps, max_pathlength, seed,
+                             train, time_limit, reset_uniforms, action_uniforms, max_episodes_per_env)
 
-    def _rollout(self, eid, p, n_envs, n_timesteps, max_pathlength, seed, train, time_limit,
-                 reset_uniforms, action_uniforms, max_episodes_per_env):
+    def _rollout(self, fn, ids, info, eid, p, n_envs, n_timesteps, max_pathlength, seed, train, time_limit,
+                 reset_uniforms, action_draws, max_episodes_per_env):
+        """Stage a rollout's parameters into p (time_limit=None keeps p's) and call the entry point `fn` with the
+        environment ids it takes; `info` is the table lookup of eid's kind."""
         p.n_envs, p.n_timesteps, p.max_pathlength = int(n_envs), int(n_timesteps), int(max_pathlength)
-        p.seed, p.train, p.time_limit = int(seed) & ((1 << 64) - 1), int(bool(train)), int(time_limit)
+        p.seed, p.train = int(seed) & ((1 << 64) - 1), int(bool(train))
+        if time_limit is not None:
+            p.time_limit = int(time_limit)
         keep = []
         if reset_uniforms is not None:
             ru = _Arg(reset_uniforms, np.float64)
@@ -486,23 +490,15 @@ class Engine:
             p.reset_uniforms = ru.ptr
             p.max_episodes_per_env = int(max_episodes_per_env)
             p.mem = ru.mem
-        if action_uniforms is not None:
-            au = _Arg(action_uniforms, np.float64)
-            keep.append(au)
-            p.action_uniforms = au.ptr
-            p.mem = au.mem
-        n = ctypes.c_int64(0)
-        paths = ctypes.c_int64(0)
-        if eid is None:
-            check(lib.trpo_rollout_cartpole(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
-                  "trpo_rollout_cartpole")
-            eid = _lib.ENV_CARTPOLE_V0
-        else:
-            check(lib.trpo_rollout_env(self._h, eid, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
-                  "trpo_rollout_env")
-        self.rollout_steps = n.value
-        self.rollout_paths = paths.value
-        self.rollout_state_dim = env_info(eid)["state_dim"]
+        if action_draws is not None:
+            ad = _Arg(action_draws, np.float64)
+            keep.append(ad)
+            p.action_uniforms = ad.ptr
+            p.mem = ad.mem
+        n, paths = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(getattr(lib, fn)(self._h, *ids, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)), fn)
+        self.rollout_steps, self.rollout_paths = n.value, paths.value
+        self.rollout_state_dim = info(eid)["state_dim"]
         self._tail_ptr = None
         return n.value, paths.value
 
@@ -565,18 +561,17 @@ class Engine:
         final_obs f64 [P,obs_dim] (the observation of s_T, the state after the last step), final_dists f32 [P,A] (the policy at
         float32(s_T) for cut-off paths, zeros otherwise), lengths i64 [P] and end_rows i64 [P] (the row of
         each path's last step)."""
+        return self._fetch_ends("trpo_rollout_fetch_ends", "final_dists")
+
+    def _fetch_ends(self, fn, head_key):
         if getattr(self, "rollout_paths", None) is None:
             # no rollout yet: the engine reports the state error
-            check(lib.trpo_rollout_fetch_ends(self._h, None, None, None, None, None, MEM_HOST),
-                  "trpo_rollout_fetch_ends")
+            check(getattr(lib, fn)(self._h, None, None, None, None, None, MEM_HOST), fn)
         P = self.rollout_paths
         out = {"truncated": np.empty(P, np.uint8), "final_obs": np.empty((P, self.obs_dim)),
-               "final_dists": np.empty((P, self.n_actions), np.float32), "lengths": np.empty(P, np.int64),
+               head_key: np.empty((P, self.n_actions), np.float32), "lengths": np.empty(P, np.int64),
                "end_rows": np.empty(P, np.int64)}
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-        check(lib.trpo_rollout_fetch_ends(self._h, ptr(out["truncated"]), ptr(out["final_obs"]),
-                                          ptr(out["final_dists"]), ptr(out["lengths"]), ptr(out["end_rows"]),
-                                          MEM_HOST), "trpo_rollout_fetch_ends")
+        check(getattr(lib, fn)(self._h, *(a.ctypes.data_as(ctypes.c_void_p) for a in out.values()), MEM_HOST), fn)
         return out
 
     def tail_view(self) -> "_lib.TailView":
@@ -623,29 +618,9 @@ class Engine:
         cid = _cont_env_id(env)
         p = _lib.RolloutParams()
         check(lib.trpo_default_rollout_params_cont(cid, ctypes.byref(p)), "trpo_default_rollout_params_cont")
-        p.n_envs, p.n_timesteps, p.max_pathlength = int(n_envs), int(n_timesteps), int(max_pathlength)
-        p.seed, p.train = int(seed) & ((1 << 64) - 1), int(bool(train))
-        if time_limit is not None:
-            p.time_limit = int(time_limit)
-        keep = []
-        if reset_uniforms is not None:
-            ru = _Arg(reset_uniforms, np.float64)
-            keep.append(ru)
-            p.reset_uniforms = ru.ptr
-            p.max_episodes_per_env = int(max_episodes_per_env)
-            p.mem = ru.mem
-        if action_normals is not None:
-            an = _Arg(action_normals, np.float64)
-            keep.append(an)
-            p.action_uniforms = an.ptr
-            p.mem = an.mem
-        n, paths = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(lib.trpo_rollout_gaussian(self._h, cid, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)),
-              "trpo_rollout_gaussian")
-        self.rollout_steps, self.rollout_paths = n.value, paths.value
-        self._tail_ptr = None
-        self.rollout_state_dim = cont_env_info(cid)["state_dim"]
-        return n.value, paths.value
+        return self._rollout("trpo_rollout_gaussian", (cid,), cont_env_info, cid, p, n_envs, n_timesteps,
+                             max_pathlength, seed, train, time_limit, reset_uniforms, action_normals,
+                             max_episodes_per_env)
 
     def rollout_gaussian_fetch(self):
         """The concatenated Gaussian rollout (host arrays): obs f64 [N,obs_dim] and obs32, actions and means f32
@@ -669,19 +644,7 @@ class Engine:
     def rollout_gaussian_fetch_ends(self):
         """rollout_fetch_ends of a Gaussian rollout: truncated, final_obs, final_means f32 [P,A] (the policy's mean
         at float32(s_T) for cut-off paths, zeros otherwise), lengths, end_rows."""
-        if getattr(self, "rollout_paths", None) is None:
-            check(lib.trpo_rollout_gaussian_fetch_ends(self._h, None, None, None, None, None, MEM_HOST),
-                  "trpo_rollout_gaussian_fetch_ends")
-        P = self.rollout_paths
-        out = {"truncated": np.empty(P, np.uint8), "final_obs": np.empty((P, self.obs_dim)),
-               "final_means": np.empty((P, self.n_actions), np.float32), "lengths": np.empty(P, np.int64),
-               "end_rows": np.empty(P, np.int64)}
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
-        check(lib.trpo_rollout_gaussian_fetch_ends(self._h, ptr(out["truncated"]), ptr(out["final_obs"]),
-                                                   ptr(out["final_means"]), ptr(out["lengths"]),
-                                                   ptr(out["end_rows"]), MEM_HOST),
-              "trpo_rollout_gaussian_fetch_ends")
-        return out
+        return self._fetch_ends("trpo_rollout_gaussian_fetch_ends", "final_means")
 
     def rollout_gaussian_to_batch(self, n_global: Optional[int] = None):
         """Load the Gaussian rollout as the feed (states, actions, old mean, the rollout's logstd, rewards, path
