@@ -571,7 +571,12 @@ int trpo_cont_env_step(int cenv, const double* state, const float* action, int64
  * predict = the net on one path's features (utils.py:87-92).  Parameters are flat in creation
  * order [W1, b1, W2, b2, W3, b3], W row-major [fan_in][fan_out]. */
 typedef struct trpo_vf trpo_vf;
-/* feat_dim = obs_dim + n_actions + 1; hidden = {64, 64} (utils.py:60-61) or NULL/0 for that default */
+/* feat_dim = obs_dim + n_actions + 1; hidden = two widths, each in [1, TRPO_VF_MAX_HIDDEN], or NULL/0 for the
+ * reference's {64, 64} (utils.py:60-61); a width outside the range is refused.  Any width in the range works, a
+ * multiple of 4 or not: the two ReLU layers and the backward run on the f32 MFMA row tiles at every width (128- or
+ * 256-column tiles past 128), the weight gradients on the f32 tiles up to fan_out 128 and on the bf16 x 3 split
+ * tiles beyond. */
+#define TRPO_VF_MAX_HIDDEN 512
 int trpo_vf_create(trpo_vf** out, int feat_dim, const int* hidden, int n_hidden, int64_t max_rows, int device);
 void trpo_vf_destroy(trpo_vf* vf);
 int64_t trpo_vf_num_params(const trpo_vf* vf);

@@ -1094,6 +1094,8 @@ void launch_wg3_cfg(const WGradArgs& a, hipStream_t s) {
 }  // namespace
 
 bool rowgemm_uses_split(int Npad, RowEpi epi) {
+  // the VF's ReLU GEMMs (vf.cpp) carry no B planes: they stay on the f32 tiles at every width
+  if (epi == RowEpi::kRelu || epi == RowEpi::kReluBwd) return false;
   return g_options.split_mfma != 0 && Npad > 128 && !epi_is_head((int)epi);
 }
 

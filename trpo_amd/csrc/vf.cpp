@@ -80,8 +80,11 @@ struct trpo_vf {
     REQUIRE(max_rows >= 1, "max_rows must be >= 1");
     REQUIRE(n_hidden == 0 || n_hidden == 2, "the VF has two hidden layers (utils.py:60-61)");
     if (n_hidden == 2) {
-      REQUIRE(hidden && hidden[0] >= 1 && hidden[1] >= 1 && hidden[0] <= 4096 && hidden[1] <= 4096,
-              "bad hidden widths");
+      // Past 256 a width only adds 256-column tiles to the row GEMMs and the weight gradients: 512 is two of
+      // them, and the suite runs a full pair of tiles (256) and a full tile next to a partial one (384).
+      REQUIRE(hidden && hidden[0] >= 1 && hidden[1] >= 1 && hidden[0] <= TRPO_VF_MAX_HIDDEN &&
+                  hidden[1] <= TRPO_VF_MAX_HIDDEN,
+              "hidden widths must be in [1, 512]");
       H1 = hidden[0];
       H2 = hidden[1];
     }
