@@ -235,6 +235,30 @@ int trpo_policy_grad(trpo_engine* e, float* g_out, int mem);
 /* fisher_vector_product(p) = session.run(self.fvp) + cg_damping * p (trpo_inksci.py:56-70,124-126) */
 int trpo_fvp(trpo_engine* e, const float* v, float* out, float damping, int mem);
 
+/* ---- Fisher-vector products on a subsample of the batch ----------------------------------
+ * The estimator of Schulman's modular_rl and OpenAI baselines' trpo_mpi (fvpargs = [arr[::5] for arr in args]),
+ * which the reference does not have.  With stride k >= 1 the Fisher rows are the feed's rows i with i % k == 0,
+ * n_sub = ceil(n / k) of them, and every Fisher-vector product the engine evaluates is
+ *   F_sub v + damping v,   F_sub = (1 / n_sub) sum_{i % k == 0} J_i^T M_i J_i
+ * (J_i the Jacobian of row i's head outputs, M_i the head's Fisher metric: the FVP above, over those rows with
+ * N = n_sub).  That is trpo_fvp, trpo_cg and, inside trpo_update, the CG products and the shs product.  Everything
+ * else still runs on all n rows: the advantages, g, the losses, every line-search trial and the kl > 2 max_kl
+ * revert.  The engine keeps the sampled rows in a child engine of ceil(max_rows / k) rows, gathered on the device
+ * whenever the feed or its advantages change; products and CG solves are bit-identical to those of a plain engine
+ * with max_rows = ceil(max_rows / k) that was fed states[::k], actions[::k], advant[::k], old[::k].
+ * k = 1 (the default) is the engine without any of this: no child, no launch, no allocation.
+ * Single-process only, for now: with k > 1 a feed whose n_global != n, trpo_comm_init and
+ * trpo_comm_set_host_allreduce fail with TRPO_ERR_STATE, and so does trpo_set_fvp_subsample(k > 1) on an engine that
+ * has a communicator or a host transport; k < 1 fails with TRPO_ERR_STATE; nothing is launched in either case.
+ * Changing k drops the captured update graph. */
+int trpo_set_fvp_subsample(trpo_engine* e, int stride);
+/* the stride in force and n_sub = ceil(n / stride) of the current feed (0 without one); either may be NULL */
+int trpo_get_fvp_subsample(trpo_engine* e, int* stride, int64_t* n_sub);
+/* The Fisher feed's rows, unpadded, for tests of the gather: states [n_sub][obs_dim] f32, actions [n_sub] int32
+ * (categorical, as the engine keeps them) or [n_sub][act_dim] f32 (Gaussian), old [n_sub][A] f32 (old_dist or
+ * old_mean), advant [n_sub] f32; any may be NULL.  TRPO_ERR_STATE when the stride is 1 or there is no feed. */
+int trpo_fvp_subsample_fetch(trpo_engine* e, float* states, void* actions, float* old, float* advant, int mem);
+
 /* ---- the numpy half --------------------------------------------------------- */
 /* conjugate_gradient(fisher_vector_product, b, cg_iters, residual_tol) (utils.py:185-201),
  * device-resident: every FVP, dot and axpy stays on the GPU. */

@@ -1,10 +1,11 @@
 """Run learn() (the reference's loop, trpo_inksci.py:89-177) on one of the built-in environments on the GPU and
 print the reference's per-iteration statistics.
-usage: python tools/learn_env.py ENV iterations n_envs [gae_lambda] [bootstrap]
+usage: python tools/learn_env.py ENV iterations n_envs [gae_lambda] [bootstrap] [fvp=K]
 ENV is CartPole-v0, MountainCar-v0 or Acrobot-v1 (trpo_amd.engine.ENVS), or a continuous-action environment under a
 diagonal-Gaussian policy: Pendulum-v1 or MountainCarContinuous-v0 (trpo_amd.engine.CONT_ENVS).  gae_lambda given: GAE(lambda) advantages
 instead of the reference's discount(rewards) - baseline; the word "bootstrap" after it: paths cut off by the time
-limit are bootstrapped from V(s_T).  Training stops at the reference's mean episode reward of 1.1*500 on
+limit are bootstrapped from V(s_T); fvp=K (anywhere after n_envs): the Fisher-vector products run on every K-th row of
+the batch (config["fvp_subsample"]).  Training stops at the reference's mean episode reward of 1.1*500 on
 CartPole-v0; the others, whose mean episode rewards stay below it, train for all the iterations asked for."""
 import os
 import sys
@@ -18,6 +19,8 @@ from trpo_amd.engine import CONT_ENVS, ENVS, cont_env_info, env_info  # noqa: E4
 
 if len(sys.argv) < 4 or (sys.argv[1] not in ENVS and sys.argv[1] not in CONT_ENVS):
     sys.exit(__doc__)
+fvp = [a for a in sys.argv[4:] if a.startswith("fvp=")]
+sys.argv = [a for a in sys.argv if not a.startswith("fvp=")]
 env = sys.argv[1]
 iters, n_envs = int(sys.argv[2]), int(sys.argv[3])
 gae_lambda = float(sys.argv[4]) if len(sys.argv) > 4 else None
@@ -32,6 +35,8 @@ else:
 config = {**CONFIG, "env": env, "gae_lambda": gae_lambda}
 if bootstrap:
     config["bootstrap_truncated"] = True
+if fvp:
+    config["fvp_subsample"] = int(fvp[-1][4:])
 # every environment can overshoot its share of the step budget by one episode
 budget = -(-config["episodes_per_roll"] // n_envs)
 max_rows = n_envs * (budget + min(config["max_steps"], info["time_limit"]) - 1)

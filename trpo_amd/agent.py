@@ -51,6 +51,10 @@ CONFIG = {"max_steps": 1000, "episodes_per_roll": 1000, "gamma": 0.95, "cg_dampi
 # MountainCarContinuous-v0): the agent then builds a diagonal-Gaussian engine, its second argument counts action
 # dimensions, "init_logstd" (default 0.0) is the initial log-std of every one, the paths feed() / update() take are
 # Gaussian paths (gaussian_paths_to_batch) and learn() rolls out with Engine.rollout_gaussian.
+# "fvp_subsample": k (absent: 1) evaluates the Fisher-vector products of update(), update_stepwise() and learn() on
+# every k-th row of the batch (Engine.set_fvp_subsample), as modular_rl and baselines' trpo_mpi do; the gradient,
+# the losses and the line search stay on all rows.  Single-process: set_ranks(world > 1) then raises the engine's
+# refusal.
 DEFAULT_ENV = "CartPole-v0"
 REWARD_TARGET = 1.1 * 500   # trpo_inksci.py:135
 
@@ -209,6 +213,8 @@ class TRPOAgent:
         self.rank, self.world, self.group = 0, 1, None
         if self.config.get("gae_lambda") is not None:
             self.engine.set_advantage_estimator("gae", self.config["gae_lambda"])
+        if self.config.get("fvp_subsample") is not None:
+            self.engine.set_fvp_subsample(int(self.config["fvp_subsample"]))
 
     def set_ranks(self, rank: int, world: int, group=None, host_allreduce: bool = False):
         """Run learn() as one of `world` ranks (one process per GPU, torch.distributed initialised by the

@@ -57,6 +57,16 @@ struct trpo_engine {
   const float* logstd_of(const float* th) const { return th + (P - w[L]); }
   std::vector<int64_t> offW, offb;
   int64_t cap = 0, n = 0, n_global = 0;
+  // Fisher subsampling (trpo_set_fvp_subsample): with a stride k > 1 the engine has a child engine, `fisher`, of
+  // ceil(cap / k) rows that holds rows 0, k, 2k, ... of the feed and serves every Fisher-vector product (fvp(), cg());
+  // k = 1: no child, nothing below runs.  The child (owner != NULL) borrows its owner's stream, so its launches fall
+  // into the owner's captured update graph, and the owner's theta and CG scalar block (sc, fl), so the update's
+  // statistics and step scaling read the CG's results where they always did; it owns every buffer with rows in it,
+  // its weight images, its CG vectors and the scalar block of its own prepare pass's losses (loss_sc).
+  int64_t fvp_stride = 1;
+  trpo_engine* fisher = nullptr;
+  trpo_engine* owner = nullptr;
+  std::string tag_prefix;   // of the child's profile tags ("sub."), in its owner's table
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
@@ -102,6 +112,7 @@ struct trpo_engine {
   double *partA = nullptr, *partB = nullptr, *part3 = nullptr, *local3 = nullptr, *dscal = nullptr;
   void* scan_ws = nullptr;
   UpdScalars* sc = nullptr;
+  UpdScalars* loss_sc = nullptr;   // where reduce_losses() stores: sc, or a child's own block
   CGFlags* fl = nullptr;
   int* dbad = nullptr;
   UpdScalars* hsc = nullptr;   // pinned host mirror
@@ -126,16 +137,20 @@ struct trpo_engine {
     bool d1_plane = false;   // D1h holds the current D_1 (row stride d1_mpad = round256(n))
     bool d1_tiled = false;   // ... with one scale per 32-row tile (eD1t, hbwd.hip) instead of pl_e[1]
     int d1_mpad = 0;
+    // the Fisher child (fvp_stride > 1): its feed holds the current feed's rows and advantages; its prepare cache
+    // was told of the current theta (fisher_ready())
+    bool fisher_fed = false;
+    bool fisher_theta = false;
 
     // theta changed: what prepare() derived from it is stale
-    void theta_changed() { prepared = false; }
+    void theta_changed() { prepared = fisher_theta = false; }
     // the batch changed: prepare()'s outputs and the returns belong to the old rows
-    void batch_changed() { prepared = have_returns = false; }
+    void batch_changed() { prepared = have_returns = fisher_fed = false; }
     // new rewards: the returns are the old ones'
     void rewards_changed() { have_returns = false; }
     // the advantages (and with them the returns) were recomputed: the prepare head's DS_L and losses are stale
     void advantages_computed() {
-      prepared = false;
+      prepared = fisher_fed = false;
       have_returns = true;
     }
     // prepare() starts over from freshly packed weights: their planes and images are rebuilt on demand, nothing
@@ -394,7 +409,7 @@ struct trpo_engine {
       if (e->prof) begin(std::string(prefix) + "_l" + std::to_string(l));
     }
     void begin(const std::string& tag) {
-      Ev ev{tag, e->take_event(), e->take_event()};
+      Ev ev{e->tag_prefix + tag, e->take_event(), e->take_event()};
       HIPCHECK(hipEventRecord(ev.a, e->stream));
       e->ev_live.push_back(ev);
       idx = (int)e->ev_live.size() - 1;
@@ -404,6 +419,15 @@ struct trpo_engine {
     }
   };
   void prof_collect() {
+    if (fisher) {   // the child's launches, in the same table under their own tags
+      fisher->prof_collect();
+      for (auto& kv : fisher->prof_acc) {
+        auto& acc = prof_acc[kv.first];
+        acc.first += kv.second.first;
+        acc.second += kv.second.second;
+      }
+      fisher->prof_acc.clear();
+    }
     if (ev_live.empty()) return;
     HIPCHECK(hipStreamSynchronize(stream));
     for (auto& ev : ev_live) {
@@ -419,7 +443,9 @@ struct trpo_engine {
   }
 
   // ------------------------------------------------------------------------
-  void init(int dist_id, int obs, const int* hidden, int nh, int A, int64_t max_rows, int dev) {
+  // parent != NULL builds a Fisher child: no stream, theta or CG scalar block of its own (see `fisher`)
+  void init(int dist_id, int obs, const int* hidden, int nh, int A, int64_t max_rows, int dev,
+            trpo_engine* parent = nullptr) {
     REQUIRE(dist_id == TRPO_DIST_CATEGORICAL || dist_id == TRPO_DIST_GAUSSIAN,
             "dist must be TRPO_DIST_CATEGORICAL or TRPO_DIST_GAUSSIAN");
     dist = dist_id;
@@ -432,7 +458,13 @@ struct trpo_engine {
     device = dev;
     use();
     HIPCHECK(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIPCHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    owner = parent;
+    if (parent) {
+      stream = parent->stream;
+      tag_prefix = "sub.";
+    } else {
+      HIPCHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    }
     w.push_back(obs);
     for (int i = 0; i < nh; ++i) w.push_back(hidden[i]);
     w.push_back(A);
@@ -448,8 +480,10 @@ struct trpo_engine {
     if (gauss()) P += A;   // the log-std vector, last in the flat layout
     cap = max_rows;
 
-    for (float** v : {&theta, &theta_prev, &theta_trial, &theta_ls, &g, &bneg, &x, &r, &p, &p2, &z, &hv,
-                      &stepdir, &fullstep, &vin, &vout})
+    if (parent) theta = parent->theta;
+    else theta = dalloc<float>(P);
+    for (float** v : {&theta_prev, &theta_trial, &theta_ls, &g, &bneg, &x, &r, &p, &p2, &z, &hv, &stepdir, &fullstep,
+                      &vin, &vout})
       *v = dalloc<float>(P);
     int maxpad = 4;
     for (int l = 0; l < L; ++l) {
@@ -527,8 +561,15 @@ struct trpo_engine {
     local3 = dalloc<double>(4);
     dscal = dalloc<double>(8);
     scan_ws = dalloc<uint8_t>(std::max(discount_workspace_bytes(cap), gae_workspace_bytes(cap)));
-    sc = dalloc<UpdScalars>(1);
-    fl = dalloc<CGFlags>(1);
+    if (parent) {
+      sc = parent->sc;
+      fl = parent->fl;
+      loss_sc = dalloc<UpdScalars>(1);
+    } else {
+      sc = dalloc<UpdScalars>(1);
+      fl = dalloc<CGFlags>(1);
+      loss_sc = sc;
+    }
     cg_ticket = dalloc<unsigned>(1);
     dbad = dalloc<int>(1);
     f16 = g_options.split_f16 != 0;
@@ -561,8 +602,10 @@ struct trpo_engine {
       logstd0 = dalloc<float>(wp[L]);
       gs_part = dalloc<double>((size_t)kGaussColBlocks * 128);
     }
-    HIPCHECK(hipHostMalloc((void**)&hsc, sizeof(UpdScalars), hipHostMallocDefault));
-    std::memset(hsc, 0, sizeof(UpdScalars));
+    if (!parent) {   // (a child never fetches scalars: its owner does)
+      HIPCHECK(hipHostMalloc((void**)&hsc, sizeof(UpdScalars), hipHostMallocDefault));
+      std::memset(hsc, 0, sizeof(UpdScalars));
+    }
     if (!gauss()) {   // the fused FVP kernels embed the softmax head
       setup_chain();
       setup_fused16();
@@ -860,6 +903,7 @@ struct trpo_engine {
     const int64_t N = roll_n;
     REQUIRE(N <= cap, "rollout has more steps than max_rows");
     REQUIRE(n_glob >= N, "n_global must be >= the rollout's steps");
+    require_fisher_feed_ok(N, n_glob);
     use();
     o.X = X;
     o.ldx = wp[0];
@@ -886,9 +930,17 @@ struct trpo_engine {
     HIPCHECK(hipStreamSynchronize(stream));
   }
 
+  void drop_fisher() {
+    if (!fisher) return;
+    fisher->release();
+    delete fisher;
+    fisher = nullptr;
+  }
+
   void release() {
     if (device >= 0) (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
+    drop_fisher();
     for (auto& ev : ev_live) {
       (void)hipEventDestroy(ev.a);
       (void)hipEventDestroy(ev.b);
@@ -902,7 +954,8 @@ struct trpo_engine {
     free_har_slots();
     if (hsc) (void)hipHostFree(hsc);
     if (comm) (void)ncclCommDestroy(comm);
-    if (stream) (void)hipStreamDestroy(stream);
+    if (stream && !owner) (void)hipStreamDestroy(stream);
+    stream = nullptr;
   }
 
   // the split geometry of the launches that follow: S (FVP weight gradients) or S_pg (policy gradient)
@@ -1225,7 +1278,7 @@ struct trpo_engine {
     launch_rowterms_partials(rowterms, n, part3, skip, stream);
     launch_rowterms_finish(part3, local3, skip, stream);
     allreduce_f64(local3, 3);
-    launch_losses_store(local3, 1.0 / (double)n_global, sc, which, skip, stream);
+    launch_losses_store(local3, 1.0 / (double)n_global, loss_sc, which, skip, stream);
     check_launch();
   }
 
@@ -1278,6 +1331,89 @@ struct trpo_engine {
       x_planes = true;
     }
     check_launch();
+  }
+
+  // ---- Fisher subsampling ----
+  static int64_t sub_rows(int64_t rows, int64_t k) { return (rows + k - 1) / k; }
+  // single-process only: the 1/N of a subsampled Fisher matrix over ranks would be sum_r ceil(n_r / k)
+  void require_fisher_feed_ok(int64_t rows, int64_t rows_global) const {
+    if (fvp_stride > 1 && rows_global != rows)
+      throw std::runtime_error("fvp_subsample = " + std::to_string(fvp_stride) + " needs n_global == n (got n = " +
+                               std::to_string(rows) + ", n_global = " + std::to_string(rows_global) +
+                               "): multi-rank subsampling is not supported");
+  }
+  void require_single_rank_for_fisher(const char* call) const {
+    if (fvp_stride > 1)
+      throw std::runtime_error(std::string(call) + ": the engine has fvp_subsample = " + std::to_string(fvp_stride) +
+                               ", which is single-process (set it back to 1 first)");
+  }
+  void set_fvp_subsample(int64_t k) {
+    REQUIRE(!owner, "a Fisher sub-engine takes no stride of its own");
+    if (k < 1) throw std::runtime_error("fvp_subsample: the stride must be >= 1, got " + std::to_string(k));
+    if (k > 1 && (comm || host_ar))
+      throw std::runtime_error(
+          "fvp_subsample > 1 is single-process: this engine has a communicator or a host all-reduce transport");
+    if (k > 1 && n > 0 && n_global != n)
+      throw std::runtime_error("fvp_subsample > 1 needs n_global == n: the current feed has n = " + std::to_string(n) +
+                               ", n_global = " + std::to_string(n_global));
+    if (k == fvp_stride) return;
+    use();
+    drop_graph();
+    HIPCHECK(hipStreamSynchronize(stream));   // nothing enqueued still reads the old child's buffers
+    drop_fisher();
+    fvp_stride = 1;
+    cache.fisher_fed = cache.fisher_theta = false;
+    if (k == 1) return;
+    auto c = std::make_unique<trpo_engine>();
+    try {
+      c->init(dist, w[0], w.data() + 1, L - 1, w[L], sub_rows(cap, k), device, this);
+    } catch (...) {
+      c->release();
+      throw;
+    }
+    c->prof = prof;
+    fisher = c.release();
+    fvp_stride = k;
+  }
+  // rows 0, k, 2k, ... of the feed into the child, one launch on the engine stream (capturable), then what a feed
+  // load runs after staging
+  void gather_fisher_feed() {
+    trpo_engine* c = fisher;
+    const int64_t ns = sub_rows(n, fvp_stride);
+    GatherArgs ga{};
+    auto wide = [&](const float* src, float* dst, int ld) { ga.wide[ga.nwide++] = GatherWide{src, dst, ld / 4, 0}; };
+    wide(X, c->X, wp[0]);
+    wide(old, c->old, wp[L]);
+    if (gauss()) wide(actf, c->actf, wp[L]);
+    else ga.scalar[ga.nscalar++] = GatherScalar{act, c->act};
+    ga.scalar[ga.nscalar++] = GatherScalar{adv32, c->adv32};
+    ga.n_sub = ns;
+    ga.stride = fvp_stride;
+    if (gauss()) {
+      ga.whole_src = logstd0;
+      ga.whole_dst = c->logstd0;
+      ga.whole_n = w[L];
+    }
+    {
+      Scope sp(this, "fisher_gather");
+      launch_gather_feed(ga, num_cus, stream);
+      check_launch();
+    }
+    c->n = c->n_global = ns;
+    c->update_x_amax();
+    c->feed_loaded();
+    cache.fisher_fed = true;
+  }
+  // the engine that serves the Fisher-vector products: this one, or the child with the current feed and theta
+  trpo_engine* fisher_ready() {
+    if (!fisher) return this;
+    require_batch();
+    if (!cache.fisher_fed) gather_fisher_feed();
+    if (!cache.fisher_theta) {
+      fisher->cache.theta_changed();
+      cache.fisher_theta = true;
+    }
+    return fisher;
   }
 
   // policy forward + KL_ff plain backward at theta (cached over CG)
@@ -2052,9 +2188,12 @@ struct trpo_engine {
     policy_grad();
     // stepdir = conjugate_gradient(fisher_vector_product, -g)  (:147)
     launch_scale_copy(g, bneg, -1.0f, P, stream);
-    cg(bneg, stepdir, prm.cg_iters, prm.residual_tol, prm.cg_damping);
+    // the Fisher matrix of the CG and of shs: over every row, or (fvp_stride > 1) over the child's rows, gathered
+    // here, after the advantages
+    trpo_engine* fe = fisher_ready();
+    fe->cg(bneg, stepdir, prm.cg_iters, prm.residual_tol, prm.cg_damping);
     // shs = .5 * stepdir.dot(fisher_vector_product(stepdir)) ; lm ; fullstep ; rate  (:148-151)
-    fvp(stepdir, hv, nullptr);
+    fe->fvp(stepdir, hv, nullptr);
     {
       Scope sp(this, "step_scale");
       launch_shs_partials(hv, stepdir, g, P, sc, partA, partB, stream);
@@ -2075,6 +2214,7 @@ struct trpo_engine {
   // and replays, later ones replay.  The cache state the prefix leaves behind is restored after a replay.
   struct GraphKey {
     int64_t n, n_global;
+    int64_t fvp_stride;   // the Fisher child's rows follow from it: its launches are part of the graph
     const void* comm;   // the communicator / host transport the all-reduces were captured with
     const void* host_ar;
     int rank, world;
@@ -2088,13 +2228,14 @@ struct trpo_engine {
     Options opt;
   };
   static_assert(offsetof(GraphKey, opt) ==
-                    2 * sizeof(int64_t) + 2 * sizeof(void*) + 8 * sizeof(int) + 2 * sizeof(float) + 2 * sizeof(double),
+                    3 * sizeof(int64_t) + 2 * sizeof(void*) + 8 * sizeof(int) + 2 * sizeof(float) + 2 * sizeof(double),
                 "GraphKey is compared with memcmp: keep it free of padding");
   GraphKey graph_key(const trpo_update_params& prm) const {
     GraphKey k;
     std::memset(&k, 0, sizeof k);
     k.n = n;
     k.n_global = n_global;
+    k.fvp_stride = fvp_stride;
     k.comm = comm;
     k.host_ar = (const void*)host_ar;
     k.rank = rank;
@@ -2116,6 +2257,7 @@ struct trpo_engine {
   GraphKey upd_key{};
   bool upd_key_seen = false, graphs_broken = false;
   CacheState upd_state{};   // `cache` as the captured prefix left it
+  CacheState upd_state_fisher{};   // ... and the Fisher child's
   void drop_graph() {
     if (upd_exec) {
       if (har_graph_end) (void)hipStreamSynchronize(stream);   // its host nodes may still be pending
@@ -2138,6 +2280,7 @@ struct trpo_engine {
       HIPCHECK(hipGraphLaunch(upd_exec, stream));
       if (har_graph_end) har_pending = true;
       cache = upd_state;
+      if (fisher) fisher->cache = upd_state_fisher;
       return;
     }
     if (!same) {
@@ -2148,8 +2291,9 @@ struct trpo_engine {
       upd_key_seen = true;
       return;
     }
-    // capture (the cache is rebuilt inside the graph, so the prefix must not skip prepare())
-    cache.prepared = false;
+    // capture (the cache is rebuilt inside the graph, so the prefix must not skip prepare(), nor the Fisher
+    // child's gather, whose feed_loaded() makes the child prepare again)
+    cache.prepared = cache.fisher_fed = false;
     hipGraph_t graph = nullptr;
     har_next = 0;
     HIPCHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
@@ -2168,11 +2312,12 @@ struct trpo_engine {
       upd_exec = nullptr;
       graphs_broken = true;
       (void)hipGetLastError();
-      cache.prepared = false;
+      cache.prepared = cache.fisher_fed = false;
       update_prefix(prm);
       return;
     }
     upd_state = cache;
+    if (fisher) upd_state_fisher = fisher->cache;
     har_graph_end = har_next;   // the graph's host nodes own these slots from now on
     HIPCHECK(hipGraphLaunch(upd_exec, stream));
     if (har_graph_end) har_pending = true;
@@ -2287,6 +2432,7 @@ int trpo_comm_init(trpo_engine* e, const uint8_t id[128], int rank, int world) {
   return guarded([&] {
     REQUIRE(e && id, "NULL argument");
     REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank/world");
+    e->require_single_rank_for_fisher("trpo_comm_init");
     e->use();
     if (e->comm) {
       NCCLCHECK(ncclCommDestroy(e->comm));
@@ -2308,6 +2454,7 @@ int trpo_comm_set_host_allreduce(trpo_engine* e, trpo_allreduce_cb cb, void* ctx
   return guarded([&] {
     REQUIRE(e && cb, "NULL argument");
     REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank/world");
+    e->require_single_rank_for_fisher("trpo_comm_set_host_allreduce");
     e->use();
     e->drop_graph();
     if (e->comm) {
@@ -2383,6 +2530,7 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
     e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_set_batch");
     REQUIRE(n > 0 && n <= e->cap, "n out of range (0 < n <= max_rows)");
     REQUIRE(n_global >= n, "n_global must be >= n");
+    e->require_fisher_feed_ok(n, n_global);
     e->use();
     e->n = n;
     e->n_global = n_global;
@@ -2414,6 +2562,7 @@ int trpo_set_batch_gaussian(trpo_engine* e, int64_t n, int64_t n_global, const f
     e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_set_batch_gaussian");
     REQUIRE(n > 0 && n <= e->cap, "n out of range (0 < n <= max_rows)");
     REQUIRE(n_global >= n, "n_global must be >= n");
+    e->require_fisher_feed_ok(n, n_global);
     e->use();
     e->n = n;
     e->n_global = n_global;
@@ -2595,7 +2744,7 @@ int trpo_fvp(trpo_engine* e, const float* v, float* out, float damping, int mem)
     REQUIRE(e && v && out, "NULL argument");
     e->use();
     e->copy_in(e->vin, v, e->P * sizeof(float), mem);
-    e->fvp(e->vin, e->hv, nullptr);
+    e->fisher_ready()->fvp(e->vin, e->hv, nullptr);
     // out = fvp + damping * v  (float32, trpo_inksci.py:126)
     HIPCHECK(hipMemcpyAsync(e->vout, e->hv, e->P * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
     if (damping != 0.0f) {
@@ -2614,7 +2763,7 @@ int trpo_cg(trpo_engine* e, const float* b, float* x_out, int cg_iters, float re
     REQUIRE(e && b && x_out, "NULL argument");
     e->use();
     e->copy_in(e->bneg, b, e->P * sizeof(float), mem);
-    e->cg(e->bneg, e->stepdir, cg_iters, residual_tol, damping);
+    e->fisher_ready()->cg(e->bneg, e->stepdir, cg_iters, residual_tol, damping);
     e->copy_out(x_out, e->stepdir, e->P * sizeof(float), mem);
     e->fetch_scalars();
     if (iters_out) *iters_out = e->hsc->iters;
@@ -2991,12 +3140,53 @@ int trpo_rollout_gaussian_to_batch(trpo_engine* e, int64_t n_global) {
   });
 }
 
+int trpo_set_fvp_subsample(trpo_engine* e, int stride) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    e->set_fvp_subsample(stride);
+  });
+}
+
+int trpo_get_fvp_subsample(trpo_engine* e, int* stride, int64_t* n_sub) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    if (stride) *stride = (int)e->fvp_stride;
+    if (n_sub) *n_sub = trpo_engine::sub_rows(e->n, e->fvp_stride);
+  });
+}
+
+int trpo_fvp_subsample_fetch(trpo_engine* e, float* states, void* actions, float* old, float* advant, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    if (!e->fisher) throw std::runtime_error("trpo_fvp_subsample_fetch: no Fisher feed (fvp_subsample is 1)");
+    e->use();
+    trpo_engine* c = e->fisher_ready();
+    const int64_t ns = c->n;
+    const int obs = c->w[0], A = c->w[c->L];
+    // padded rows -> the caller's unpadded ones, through the child's staging buffer for a host caller
+    auto rows = [&](const float* src, int width, int ld, float* out) {
+      if (!out) return;
+      float* dst = mem == TRPO_MEM_DEVICE ? out : c->stage;
+      launch_copy_rows(src, ns, width, ld, dst, width, c->stream);
+      check_launch();
+      if (mem != TRPO_MEM_DEVICE) e->copy_out(out, c->stage, (size_t)ns * width * sizeof(float), mem);
+    };
+    rows(c->X, obs, c->wp[0], states);
+    rows(c->old, A, c->wp[c->L], old);
+    if (c->gauss()) rows(c->actf, A, c->wp[c->L], static_cast<float*>(actions));
+    else if (actions) e->copy_out(actions, c->act, (size_t)ns * sizeof(int), mem);
+    if (advant) e->copy_out(advant, c->adv32, (size_t)ns * sizeof(float), mem);
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
 int trpo_profile_enable(trpo_engine* e, int enable) {
   return guarded([&] {
     REQUIRE(e, "engine is NULL");
     e->use();
     e->prof_collect();
     e->prof = enable != 0;
+    if (e->fisher) e->fisher->prof = e->prof;
   });
 }
 

@@ -372,6 +372,30 @@ void launch_amax(const float* A, int64_t n, int w, int ld, unsigned* out, hipStr
 void launch_copy_rows(const float* src, int64_t n, int w, int ld_src, float* dst, int ld_dst, hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// the Fisher feed's gather (gather.hip): dst row i = src row i * stride, i < n_sub, for every array in one launch
+// ---------------------------------------------------------------------------
+struct GatherWide {
+  const void* src;   // rows of q 16-byte units, 16-byte-aligned base
+  void* dst;
+  int q, pad;
+};
+struct GatherScalar {
+  const void* src;   // one 4-byte element per row
+  void* dst;
+};
+struct GatherArgs {
+  GatherWide wide[3];
+  GatherScalar scalar[2];
+  int nwide, nscalar;
+  int64_t n_sub, stride;
+  const float* whole_src;   // copied whole (the old log-std vector), whole_n floats
+  float* whole_dst;
+  int64_t whole_n;
+};
+// grid sized from num_cus; the caller guarantees (n_sub - 1) * stride < the source's rows
+void launch_gather_feed(const GatherArgs& a, int num_cus, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // discount scan + standardisation (scan.hip)
 // ---------------------------------------------------------------------------
 // out[t] = x[t] + gamma*out[t+1] within episodes (starts[t] = 1 begins an episode)

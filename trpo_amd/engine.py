@@ -389,6 +389,34 @@ class Engine:
         check(lib.trpo_fvp(self._h, vi.ptr, a.ptr, float(damping), vi.mem), "trpo_fvp")
         return res
 
+    def set_fvp_subsample(self, k: int):
+        """Evaluate every Fisher-vector product (fvp, cg, and the CG and shs products inside update) on rows
+        0, k, 2k, ... of the feed, F_sub v + damping v; everything else stays on all rows.  k = 1 (the default)
+        is the plain engine.  Single-process only (include/trpo_engine.h)."""
+        check(lib.trpo_set_fvp_subsample(self._h, int(k)), "trpo_set_fvp_subsample")
+
+    @property
+    def fvp_subsample(self):
+        """(k, n_sub): the stride in force and ceil(n / k) of the current feed."""
+        k, ns = ctypes.c_int(0), ctypes.c_int64(0)
+        check(lib.trpo_get_fvp_subsample(self._h, ctypes.byref(k), ctypes.byref(ns)), "trpo_get_fvp_subsample")
+        return k.value, ns.value
+
+    def fvp_subsample_fetch(self) -> dict:
+        """The Fisher feed as the engine holds it (host copies, unpadded): states, actions (int64 [n_sub], or
+        float32 [n_sub, A] on a Gaussian engine), old (old_dist / old_mean) and advant.  For tests of the gather."""
+        _, ns = self.fvp_subsample
+        A = self.n_actions
+        states = np.empty((ns, self.obs_dim), np.float32)
+        old = np.empty((ns, A), np.float32)
+        adv = np.empty(ns, np.float32)
+        act = np.empty((ns, A), np.float32) if self._gaussian else np.empty(ns, np.int32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        check(lib.trpo_fvp_subsample_fetch(self._h, ptr(states), ptr(act), ptr(old), ptr(adv), MEM_HOST),
+              "trpo_fvp_subsample_fetch")
+        return {"states": states, "actions": act if self._gaussian else act.astype(np.int64), "old": old,
+                "advant": adv}
+
     def cg(self, b, cg_iters=10, residual_tol=1e-10, damping=0.1, out=None):
         bi = _Arg(b, np.float32, (self.num_params,))
         res, a = self._out(out, np.float32, self.num_params)
