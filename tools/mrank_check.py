@@ -2,6 +2,7 @@
 
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29555 \
         tools/mrank_check.py [--host-allreduce] [--dims c3|c4|c5|g17] [--dist gaussian] [--rows N] [--graphs]
+        [--max-kl X] [--residual-tol T] [--adv-scale S] [--expect ITERS,K,REVERTED]
 
 --host-allreduce  ranks share a GPU (RCCL refuses duplicate devices): the engine's all-reduces run
                   through its stream-ordered host transport, summed by gloo on the host
@@ -13,7 +14,13 @@
                   is (17, [64, 64], 6) and c4 is read as (128, [256, 256], 17); the cut between the ranks is uneven
                   (shard_bounds moved to the next multiple of 173 rows); stepdir is held to 1e-5 too, and the
                   log-std tail of Hv, theta and stepdir also on its own
-Checks: ranks bitwise identical; Hv and theta within 1e-5 of one rank holding all rows; same k.
+--max-kl, --residual-tol   the update's parameters (defaults 0.01 and 0: ten CG iterations, k = 0): with them the
+                  update stops CG early, backtracks or rejects every trial, on every rank at the same place
+--adv-scale S     the advantages times S (rdotr times S^2: another stop under the same tol); S != 1 feeds the
+                  categorical engine the standardised advantages directly instead of the rewards
+--expect I,K,R    what cg_iters, k and reverted must be (tests/update_outcomes_ref.py's float64 reference)
+Checks: ranks bitwise identical (theta, stepdir, the update's stats); Hv and theta within 1e-5 of one rank holding
+all rows; the same cg_iters, k and reverted as that rank.
 """
 import argparse
 import os
@@ -35,6 +42,10 @@ def main():
     ap.add_argument("--rows", type=int, default=40_000)
     ap.add_argument("--graphs", action="store_true")
     ap.add_argument("--dist", default="categorical", choices=["categorical", "gaussian"])
+    ap.add_argument("--max-kl", type=float, default=0.01)
+    ap.add_argument("--residual-tol", type=float, default=0.0)
+    ap.add_argument("--adv-scale", type=float, default=1.0)
+    ap.add_argument("--expect", default=None)
     args = ap.parse_args()
     gauss = args.dist == "gaussian"
     if gauss != (args.dims == "g17") and args.dims != "c4":
@@ -62,27 +73,33 @@ def main():
         # theta_old = theta: the whole-update feed, the advantages given directly (standardised over all rows)
         spec, theta, gb = G.make_case((obs, hidden, A, n), seed=3, perturb=0.0)
         starts = (np.arange(n) % 173 == 0).astype(np.uint8)    # an uneven cut: the next multiple of 173 rows
-        prm = UpdateParams(residual_tol=0.0)
+        prm = UpdateParams(residual_tol=args.residual_tol, max_kl=args.max_kl)
+        gadv = (gb.advant.astype(np.float64) * args.adv_scale).astype(np.float32)
 
         def new_engine(rows):
             return Engine(obs, hidden, A, max_rows=rows, device=dev, dist="gaussian")
 
         def feed(e, lo, hi):
             e.set_flat(theta)
-            e.set_batch_gaussian(gb.X[lo:hi], gb.actions[lo:hi], gb.advant[lo:hi], gb.old_mean[lo:hi], gb.old_logstd,
+            e.set_batch_gaussian(gb.X[lo:hi], gb.actions[lo:hi], gadv[lo:hi], gb.old_mean[lo:hi], gb.old_logstd,
                                  n_global=n)
     else:
         obs, hidden, A = DIMS[args.dims]
         spec = O.PolicySpec(obs, hidden, A)
         d = O.synthetic_batch(spec, n, seed=3, episode_len=200)
         theta, starts = d["theta"], d["starts"]
-        prm = UpdateParams(residual_tol=0.0, compute_advantages=True)
+        from_rewards = args.adv_scale == 1.0
+        prm = UpdateParams(residual_tol=args.residual_tol, max_kl=args.max_kl, compute_advantages=from_rewards)
+        cadv = (d["advant"] * args.adv_scale).astype(np.float32)     # standardised over all rows
 
         def new_engine(rows):
             return Engine(spec.obs_dim, spec.hidden, spec.n_actions, max_rows=rows, device=dev)
 
         def feed(e, lo, hi):
             e.set_flat(theta)
+            if not from_rewards:
+                e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], cadv[lo:hi], d["old_dist"][lo:hi], n_global=n)
+                return
             e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], None, d["old_dist"][lo:hi], n_global=n)
             e.set_rewards(d["rewards"][lo:hi], d["starts"][lo:hi])
             e.compute_advantages(0.95)
@@ -118,10 +135,11 @@ def main():
         assert stg == st, f"rank {rank}: graph update {i} stats differ: {stg} vs {st}"
     # every rank must hold the same parameters; compare with a single-engine run on rank 0
     allth = [None] * world
-    dist.all_gather_object(allth, th)
+    dist.all_gather_object(allth, (th, sd, st))
     if rank == 0:
-        for t in allth[1:]:
-            assert np.array_equal(t, allth[0]), "ranks diverged"
+        for t, s_, st_ in allth[1:]:
+            assert np.array_equal(t, allth[0][0]) and np.array_equal(s_, allth[0][1]), "ranks diverged"
+            assert st_ == allth[0][2], f"ranks' stats diverged: {st_} vs {allth[0][2]}"
         e1 = new_engine(n)
         feed(e1, 0, n)
         hv1 = e1.fvp(v, 0.0)
@@ -130,9 +148,13 @@ def main():
         r1 = np.linalg.norm(hv - hv1) / np.linalg.norm(hv1)
         r2 = np.linalg.norm(th - th1) / np.linalg.norm(th1)
         print(f"world={world} dims={args.dims} rows={n} FVP rel {r1:.2e} theta rel {r2:.2e} "
-              f"k={st['k']}/{st1['k']} iters={st['cg_iters']}/{st1['cg_iters']} graph replays={len(replays)}",
-              flush=True)
+              f"k={st['k']}/{st1['k']} iters={st['cg_iters']}/{st1['cg_iters']} "
+              f"reverted={st['reverted']}/{st1['reverted']} graph replays={len(replays)}", flush=True)
         assert r1 < 1e-5 and r2 < 1e-5 and st["k"] == st1["k"]
+        assert st["cg_iters"] == st1["cg_iters"] and st["reverted"] == st1["reverted"]
+        if args.expect:
+            want = tuple(int(x) for x in args.expect.split(","))
+            assert (st["cg_iters"], st["k"], st["reverted"]) == want, (st, want)
         if gauss:
             t1 = np.linalg.norm(hv[-A:] - hv1[-A:]) / np.linalg.norm(hv1[-A:])
             t2 = np.linalg.norm(th[-A:] - th1[-A:]) / np.linalg.norm(th1[-A:])
