@@ -247,13 +247,38 @@ int trpo_fvp(trpo_engine* e, const float* v, float* out, float damping, int mem)
  * whenever the feed or its advantages change; products and CG solves are bit-identical to those of a plain engine
  * with max_rows = ceil(max_rows / k) that was fed states[::k], actions[::k], advant[::k], old[::k].
  * k = 1 (the default) is the engine without any of this: no child, no launch, no allocation.
- * Single-process only, for now: with k > 1 a feed whose n_global != n, trpo_comm_init and
+ * This entry point (the local mode) is single-process only: with k > 1 a feed whose n_global != n, trpo_comm_init and
  * trpo_comm_set_host_allreduce fail with TRPO_ERR_STATE, and so does trpo_set_fvp_subsample(k > 1) on an engine that
  * has a communicator or a host transport; k < 1 fails with TRPO_ERR_STATE; nothing is launched in either case.
- * Changing k drops the captured update graph. */
+ * Changing k, or the mode (below), drops the captured update graph. */
 int trpo_set_fvp_subsample(trpo_engine* e, int stride);
-/* the stride in force and n_sub = ceil(n / stride) of the current feed (0 without one); either may be NULL */
+/* The same child engine with the stride taken over GLOBAL row indices, for a batch sharded over ranks.  Rank r holds
+ * rows [o_r, o_r + n_r) of a global batch of n_global rows (o_r: trpo_set_row_offset).  Its Fisher rows are the local
+ * rows i with (o_r + i) % k == 0:
+ *   phase_r = (k - o_r % k) % k                          the first local Fisher row
+ *   n_sub_r = ceil((n_r - phase_r) / k) if n_r > phase_r, else 0
+ *   N_sub   = ceil(n_global / k)                          known to every rank without a collective
+ * and the rank's partial of every Fisher-vector product is scaled by 1 / N_sub and all-reduced like the full one.
+ * When the ranks' shards tile [0, n_global), sum_r n_sub_r = N_sub and the product is the single-process
+ * trpo_set_fvp_subsample(k) product on the concatenated batch, up to summation order.  Offsets that tile the batch
+ * are the caller's responsibility: the engine checks only its own shard against n_global.  With offset 0 and
+ * n_global == n this is the local mode's rows 0, k, 2k, ...
+ * Allowed with a communicator or a host transport, set before or after it; the child's all-reduces go through its
+ * owner's transport.  An engine needs n > 0, the child included, so a rank without a Fisher row is refused, not
+ * supported.  A feed with row0 + n > n_global or n <= phase fails with TRPO_ERR_STATE, nothing launched and the
+ * previous feed left in place; so does this call when the current feed is such a feed.  k = 1 is the plain engine. */
+int trpo_set_fvp_subsample_global(trpo_engine* e, int stride);
+/* row0 >= 0: the global index of the first row of the feeds that follow (trpo_set_batch, trpo_set_batch_gaussian,
+ * trpo_rollout_to_batch, trpo_rollout_gaussian_to_batch); the default is 0.  The current feed keeps the offset it was
+ * loaded with.  Outside the global mode it is recorded and has no effect: no launch, no byte.  row0 < 0 fails with
+ * TRPO_ERR_STATE. */
+int trpo_set_row_offset(trpo_engine* e, int64_t row0);
+/* the stride in force and this engine's Fisher rows of the current feed, n_sub = ceil(n / stride) or in the global
+ * mode n_sub_r (0 without a feed); either may be NULL */
 int trpo_get_fvp_subsample(trpo_engine* e, int* stride, int64_t* n_sub);
+/* the mode (1 = global rows), N_sub = ceil(n_global / stride) (local mode: n_sub), the current feed's phase (local
+ * mode: 0) and the row offset set for the next feeds; any may be NULL */
+int trpo_get_fvp_subsample_global(trpo_engine* e, int* global, int64_t* n_sub_global, int64_t* phase, int64_t* row0);
 /* The Fisher feed's rows, unpadded, for tests of the gather: states [n_sub][obs_dim] f32, actions [n_sub] int32
  * (categorical, as the engine keeps them) or [n_sub][act_dim] f32 (Gaussian), old [n_sub][A] f32 (old_dist or
  * old_mean), advant [n_sub] f32; any may be NULL.  TRPO_ERR_STATE when the stride is 1 or there is no feed. */

@@ -4,6 +4,7 @@
 
     python tools/fvp_subsample_timing.py [--cases c3,c4,gauss] [--rounds 3] [--updates 3]
                                          [--out profiles/fvp_subsample/timing.json]
+    python tools/fvp_subsample_timing.py --gather [--cases c4] [--out profiles/fvp_subsample_ranks/gather_timing.json]
 
 Cases: c3 (17 -> 64 -> 64 -> 6, 1M rows), c4 (128 -> 256 -> 256 -> 17, 8M rows) and gauss (the diagonal-Gaussian head
 at (17, [64, 64], 6), 1M rows).  One engine per case is alive at a time; a round sets each stride in turn on it (which
@@ -11,6 +12,11 @@ rebuilds the Fisher child and drops the update graph), runs three warm-up update
 times `updates` more (host clock around Engine.update, which ends in a device synchronise; every update starts from
 the same theta and computes its advantages, so the gather runs inside the replayed graph).  After the rounds one
 profiled update per stride gives the gather's milliseconds, the child's prepare pass and its FVP launches.
+
+--gather times the gather launch alone at k = 5: the local mode (first row 0) against the global mode
+(set_fvp_subsample(5, rows="global")) of the same feed loaded at row offsets 3 and 1 (first rows 2 and 4), n_global =
+rows + 5, no transport.  It reads the same number of bytes at another start, so the times should agree.  One engine;
+`--updates` profiled updates per mode, the modes alternating over `--rounds`.
 """
 import argparse
 import json
@@ -40,8 +46,9 @@ def init_theta(widths, rng, tail=0):
     return np.concatenate(parts).astype(np.float32)
 
 
-def make_engine(dist, obs, hidden, A, n, seed=1):
-    """An engine with a steady-state feed (pi_old = the policy at theta) built on the device, and its theta."""
+def make_engine(dist, obs, hidden, A, n, seed=1, with_refeed=False):
+    """An engine with a steady-state feed (pi_old = the policy at theta) built on the device, and its theta; with_refeed
+    also a function (n_global, row_offset) that loads the same feed again as a shard of a larger batch."""
     import torch
     from trpo_amd import Engine
     dev = torch.device("cuda:0")
@@ -64,6 +71,10 @@ def make_engine(dist, obs, hidden, A, n, seed=1):
         mean = torch.from_numpy(mean).to(dev)
         actions = mean + torch.exp(logstd) * torch.randn((n, A), generator=gen, device=dev, dtype=torch.float32)
         eng.set_batch_gaussian(X, actions, zeros, mean, logstd)
+
+        def refeed(n_global, row_offset):
+            eng.set_batch_gaussian(X, actions, zeros, mean, logstd, n_global=n_global, row_offset=row_offset)
+            eng.set_rewards(rewards, starts)
     else:
         actions = torch.randint(0, A, (n,), generator=gen, device=dev, dtype=torch.int64)
         uniform = torch.full((n, A), 1.0 / A, device=dev, dtype=torch.float32)
@@ -71,9 +82,14 @@ def make_engine(dist, obs, hidden, A, n, seed=1):
         old = torch.empty((n, A), device=dev, dtype=torch.float32)
         eng.action_dist(out=old)
         eng.set_batch(X, actions, zeros, old)
+
+        def refeed(n_global, row_offset):
+            eng.set_batch(X, actions, zeros, old, n_global=n_global, row_offset=row_offset)
+            eng.set_rewards(rewards, starts)
     eng.set_rewards(rewards, starts)
     torch.cuda.synchronize()
-    return eng, torch.from_numpy(theta).to(dev)
+    theta_dev = torch.from_numpy(theta).to(dev)
+    return (eng, theta_dev, refeed) if with_refeed else (eng, theta_dev)
 
 
 def timed(engine, theta, updates):
@@ -107,12 +123,47 @@ def profiled(engine, theta):
             "total_ms": round(sum(tags.values()), 4), "tags": tags}
 
 
+def gather_timing(case, rounds, updates):
+    from trpo_amd import UpdateParams
+    dist, obs, hidden, A, n = CASES[case]
+    eng, theta, refeed = make_engine(dist, obs, hidden, A, n, with_refeed=True)
+    k = 5
+    modes = (("local", None), ("global", 3), ("global", 1))
+    ms = {m: [] for m in modes}
+    eng.profile_enable(True)
+    for _ in range(rounds):
+        for mode in modes:
+            rows, offset = mode
+            eng.set_fvp_subsample(1)
+            if offset is None:
+                refeed(n, 0)
+            else:
+                refeed(n + k, offset)
+            eng.set_fvp_subsample(k, rows=rows)
+            for _u in range(updates):
+                eng.profile_reset()
+                eng.set_flat(theta)
+                eng.update(UpdateParams(cg_iters=10, residual_tol=0.0, compute_advantages=True))
+                count, total = eng.profile_query()["fisher_gather"]
+                ms[mode].append(total / count)
+    eng.close()
+    out = {"case": case, "dims": [obs, hidden, A], "rows": n, "stride": k, "modes": []}
+    for (rows, offset), v in ms.items():
+        phase = 0 if offset is None else (k - offset % k) % k
+        out["modes"].append({"rows": rows, "row_offset": offset or 0, "first_row": phase,
+                             "gather_ms_median": round(float(np.median(v)), 4),
+                             "gather_ms_min": round(float(np.min(v)), 4), "gather_ms_max": round(float(np.max(v)), 4),
+                             "launches": len(v)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="c3,c4,gauss")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--updates", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--gather", action="store_true")
     args = ap.parse_args()
     import torch
     # torch bundles its own HIP runtime, which cannot start after the engine library's: it goes first
@@ -120,7 +171,11 @@ def main():
         raise SystemExit("fvp_subsample_timing: no GPU visible")
     torch.zeros(1, device="cuda:0")
     results = []
-    for case in args.cases.split(","):
+    for case in args.cases.split(",") if args.gather else ():
+        res = gather_timing(case, args.rounds, args.updates)
+        print(json.dumps(res), flush=True)
+        results.append(res)
+    for case in () if args.gather else args.cases.split(","):
         dist, obs, hidden, A, n = CASES[case]
         eng, theta = make_engine(dist, obs, hidden, A, n)
         rounds = {k: [] for k in STRIDES}

@@ -2,7 +2,7 @@
 
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29555 \
         tools/mrank_check.py [--host-allreduce] [--dims c3|c4|c5|g17] [--dist gaussian] [--rows N] [--graphs]
-        [--max-kl X] [--residual-tol T] [--adv-scale S] [--expect ITERS,K,REVERTED]
+        [--max-kl X] [--residual-tol T] [--adv-scale S] [--expect ITERS,K,REVERTED] [--fvp-subsample K]
 
 --host-allreduce  ranks share a GPU (RCCL refuses duplicate devices): the engine's all-reduces run
                   through its stream-ordered host transport, summed by gloo on the host
@@ -19,6 +19,10 @@
 --adv-scale S     the advantages times S (rdotr times S^2: another stop under the same tol); S != 1 feeds the
                   categorical engine the standardised advantages directly instead of the rewards
 --expect I,K,R    what cg_iters, k and reverted must be (tests/update_outcomes_ref.py's float64 reference)
+--fvp-subsample K  the Fisher-vector products on every K-th row by global row index (set_fvp_subsample(K,
+                  rows="global"), each rank feeding its shard with row_offset = its first row); the one-rank
+                  comparison uses the local set_fvp_subsample(K) on all rows, and the ranks' Fisher feeds, concatenated
+                  in rank order, must be X[::K], actions[::K], old[::K] and advant[::K] of the whole feed bit for bit
 Checks: ranks bitwise identical (theta, stepdir, the update's stats); Hv and theta within 1e-5 of one rank holding
 all rows; the same cg_iters, k and reverted as that rank.
 """
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--residual-tol", type=float, default=0.0)
     ap.add_argument("--adv-scale", type=float, default=1.0)
     ap.add_argument("--expect", default=None)
+    ap.add_argument("--fvp-subsample", type=int, default=1)
     args = ap.parse_args()
     gauss = args.dist == "gaussian"
     if gauss != (args.dims == "g17") and args.dims != "c4":
@@ -63,7 +68,7 @@ def main():
     torch.cuda.set_device(dev)
     from trpo_amd import Engine, UpdateParams
     from trpo_amd._lib import VEC_STEPDIR, get_option, set_option
-    from trpo_amd.dist import init_engine_comm, shard_bounds
+    from trpo_amd.dist import fisher_rows, init_engine_comm, shard_bounds
     from oracle import trpo_oracle as O
     n = args.rows
     if gauss:
@@ -79,10 +84,10 @@ def main():
         def new_engine(rows):
             return Engine(obs, hidden, A, max_rows=rows, device=dev, dist="gaussian")
 
-        def feed(e, lo, hi):
+        def feed(e, lo, hi, n_global=n, row_offset=None):
             e.set_flat(theta)
             e.set_batch_gaussian(gb.X[lo:hi], gb.actions[lo:hi], gadv[lo:hi], gb.old_mean[lo:hi], gb.old_logstd,
-                                 n_global=n)
+                                 n_global=n_global, row_offset=row_offset)
     else:
         obs, hidden, A = DIMS[args.dims]
         spec = O.PolicySpec(obs, hidden, A)
@@ -95,12 +100,14 @@ def main():
         def new_engine(rows):
             return Engine(spec.obs_dim, spec.hidden, spec.n_actions, max_rows=rows, device=dev)
 
-        def feed(e, lo, hi):
+        def feed(e, lo, hi, n_global=n, row_offset=None):
             e.set_flat(theta)
             if not from_rewards:
-                e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], cadv[lo:hi], d["old_dist"][lo:hi], n_global=n)
+                e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], cadv[lo:hi], d["old_dist"][lo:hi], n_global=n_global,
+                            row_offset=row_offset)
                 return
-            e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], None, d["old_dist"][lo:hi], n_global=n)
+            e.set_batch(d["X"][lo:hi], d["actions"][lo:hi], None, d["old_dist"][lo:hi], n_global=n_global,
+                        row_offset=row_offset)
             e.set_rewards(d["rewards"][lo:hi], d["starts"][lo:hi])
             e.compute_advantages(0.95)
     lo, hi = shard_bounds(n, world, starts)[rank]
@@ -112,7 +119,10 @@ def main():
         e.comm_set_host_allreduce(ar, rank, world)
     else:
         init_engine_comm(e, rank, world)
-    feed(e, lo, hi)
+    K = args.fvp_subsample
+    if K > 1:
+        e.set_fvp_subsample(K, rows="global")
+    feed(e, lo, hi, row_offset=lo if K > 1 else None)
     v = np.random.RandomState(1).standard_normal(spec.n_params).astype(np.float32)
     hv = e.fvp(v, 0.0)
     saved = get_option("graphs")
@@ -136,12 +146,32 @@ def main():
     # every rank must hold the same parameters; compare with a single-engine run on rank 0
     allth = [None] * world
     dist.all_gather_object(allth, (th, sd, st))
+    fishers = [None] * world
+    if K > 1:
+        k_, ns, N_sub, phase = e.fvp_subsample_global
+        assert (k_, N_sub) == (K, -(-n // K)) and (phase, ns) == fisher_rows(hi - lo, lo, K), (k_, ns, N_sub, phase)
+        dist.all_gather_object(fishers, e.fvp_subsample_fetch())
     if rank == 0:
         for t, s_, st_ in allth[1:]:
             assert np.array_equal(t, allth[0][0]) and np.array_equal(s_, allth[0][1]), "ranks diverged"
             assert st_ == allth[0][2], f"ranks' stats diverged: {st_} vs {allth[0][2]}"
         e1 = new_engine(n)
+        if K > 1:
+            e1.set_fvp_subsample(K)
         feed(e1, 0, n)
+        if K > 1:
+            # the ranks' Fisher feeds in rank order are every K-th row of the whole feed (after the update: the
+            # advantages are the standardised ones of all rows)
+            whole = e1.fvp_subsample_fetch()
+            if gauss:
+                want = {"states": gb.X[::K], "actions": gb.actions[::K], "old": gb.old_mean[::K], "advant": gadv[::K]}
+            else:
+                want = {"states": d["X"][::K], "actions": d["actions"][::K], "old": d["old_dist"][::K],
+                        "advant": whole["advant"] if from_rewards else cadv[::K]}
+            for key, w_ in want.items():
+                got = np.concatenate([f[key] for f in fishers])
+                assert got.shape == w_.shape and np.array_equal(got, w_), f"Fisher feed: {key} is not [::{K}]"
+                assert np.array_equal(whole[key], w_), f"one-rank Fisher feed: {key} is not [::{K}]"
         hv1 = e1.fvp(v, 0.0)
         st1 = e1.update(prm)
         th1 = e1.get_flat()

@@ -117,6 +117,10 @@ SIGNATURES = {
     "trpo_policy_grad": (c_int, [c_void_p, c_void_p, c_int]),
     "trpo_fvp": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int]),
     "trpo_set_fvp_subsample": (c_int, [c_void_p, c_int]),
+    "trpo_set_fvp_subsample_global": (c_int, [c_void_p, c_int]),
+    "trpo_set_row_offset": (c_int, [c_void_p, c_int64]),
+    "trpo_get_fvp_subsample_global": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64), POINTER(c_int64),
+                                              POINTER(c_int64)]),
     "trpo_get_fvp_subsample": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64)]),
     "trpo_fvp_subsample_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "trpo_cg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, POINTER(c_int), c_int]),

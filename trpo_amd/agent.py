@@ -34,6 +34,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from ._lib import VEC_THETA_LS
 from .engine import CONT_ENVS, Engine, UpdateParams, cont_env_info, env_info
 from .vf import VF
 from .utils import (EngineLoss, GetFlat, KLFirstFixedGVP, SetFromFlat, SurrogateLoss, conjugate_gradient,
@@ -54,7 +55,9 @@ CONFIG = {"max_steps": 1000, "episodes_per_roll": 1000, "gamma": 0.95, "cg_dampi
 # "fvp_subsample": k (absent: 1) evaluates the Fisher-vector products of update(), update_stepwise() and learn() on
 # every k-th row of the batch (Engine.set_fvp_subsample), as modular_rl and baselines' trpo_mpi do; the gradient,
 # the losses and the line search stay on all rows.  Single-process: set_ranks(world > 1) then raises the engine's
-# refusal.
+# refusal, unless "fvp_subsample_rows": "global" (absent: "local") takes the stride over the rows' global indices
+# (Engine.set_fvp_subsample(k, rows="global"), trpo_amd.dist.fisher_rows): learn() then hands each rank's rollout
+# feed its row offset, and feed() / update() / update_stepwise() take one next to n_global.
 DEFAULT_ENV = "CartPole-v0"
 REWARD_TARGET = 1.1 * 500   # trpo_inksci.py:135
 
@@ -214,7 +217,8 @@ class TRPOAgent:
         if self.config.get("gae_lambda") is not None:
             self.engine.set_advantage_estimator("gae", self.config["gae_lambda"])
         if self.config.get("fvp_subsample") is not None:
-            self.engine.set_fvp_subsample(int(self.config["fvp_subsample"]))
+            self.engine.set_fvp_subsample(int(self.config["fvp_subsample"]),
+                                          rows=self.config.get("fvp_subsample_rows", "local"))
 
     def set_ranks(self, rank: int, world: int, group=None, host_allreduce: bool = False):
         """Run learn() as one of `world` ranks (one process per GPU, torch.distributed initialised by the
@@ -259,15 +263,30 @@ class TRPOAgent:
             dist.all_reduce(t, group=self.group)
         return a
 
-    def feed(self, paths_or_batch, n_global: Optional[int] = None):
-        """The feed dict of trpo_inksci.py:119-122 (+ rewards for :102-117)."""
+    def _rank_rows(self, n: int):
+        """(n_global, row_offset) of this rank's n rows: one gloo all-gather of the ranks' row counts, the offset
+        their exclusive prefix in rank order; one rank: (n, 0) and no collective."""
+        if self.world <= 1:
+            return int(n), 0
+        import torch
+        import torch.distributed as dist
+        mine = torch.tensor([int(n)], dtype=torch.int64)
+        every = [torch.zeros(1, dtype=torch.int64) for _ in range(self.world)]
+        dist.all_gather(every, mine, group=self.group)
+        counts = [int(t[0]) for t in every]
+        return sum(counts), sum(counts[:self.rank])
+
+    def feed(self, paths_or_batch, n_global: Optional[int] = None, row_offset: Optional[int] = None):
+        """The feed dict of trpo_inksci.py:119-122 (+ rewards for :102-117).  row_offset: the global index of the
+        batch's first row (config["fvp_subsample_rows"] = "global")."""
         if self.continuous:
             b = gaussian_paths_to_batch(paths_or_batch) if isinstance(paths_or_batch, list) else paths_or_batch
             self.engine.set_batch_gaussian(b["state"], b["action"], b.get("advant"), b["action_mean"], b["logstd"],
-                                           n_global)
+                                           n_global, row_offset=row_offset)
         else:
             b = paths_to_batch(paths_or_batch) if isinstance(paths_or_batch, list) else paths_or_batch
-            self.engine.set_batch(b["state"], b["action"], b.get("advant"), b["action_dist"], n_global)
+            self.engine.set_batch(b["state"], b["action"], b.get("advant"), b["action_dist"], n_global,
+                                  row_offset=row_offset)
         if "rewards" in b:
             self.engine.set_rewards(b["rewards"], b["starts"], b.get("baseline"))
             if b.get("tail_values") is not None:
@@ -275,17 +294,18 @@ class TRPOAgent:
         return b
 
     def update(self, paths_or_batch, n_global: Optional[int] = None, cg_iters: int = 10,
-               residual_tol: float = 1e-10) -> dict:
+               residual_tol: float = 1e-10, row_offset: Optional[int] = None) -> dict:
         """trpo_inksci.py:101-158 as one device call."""
-        b = self.feed(paths_or_batch, n_global)
+        b = self.feed(paths_or_batch, n_global, row_offset)
         prm = UpdateParams(cg_iters=cg_iters, residual_tol=residual_tol,
                            cg_damping=self.config["cg_damping"], max_kl=self.config["max_kl"],
                            compute_advantages="rewards" in b, gamma=self.config["gamma"])
         return self.engine.update(prm)
 
-    def update_stepwise(self, paths_or_batch, n_global: Optional[int] = None) -> dict:
+    def update_stepwise(self, paths_or_batch, n_global: Optional[int] = None,
+                        row_offset: Optional[int] = None) -> dict:
         """trpo_inksci.py:101-158 line for line over the utils surface."""
-        b = self.feed(paths_or_batch, n_global)
+        b = self.feed(paths_or_batch, n_global, row_offset)
         if "rewards" in b:
             self.engine.compute_advantages(self.config["gamma"])      # :102-117
         fisher_vector_product = self.fvp.damped(self.config["cg_damping"])                   # :124-126
@@ -319,7 +339,8 @@ class TRPOAgent:
         of iteration i's rollout (env.reset and cat_sample; tests), else a Philox stream per iteration.
         On a continuous-action environment the rollout calls are the Gaussian ones: draws(i)'s second entry is
         then the standard normals of the act, and the record's "rollout" / "ends" are the Gaussian fetch dicts.
-        record=True also returns each iteration's rollout arrays, baselines, returns and
+        record=True also returns each iteration's parameters (theta_before, theta, theta_ls: the line search's
+        point before a revert), rollout arrays, baselines, returns and
         standardised advantages, and how its paths ended ("ends", Engine.rollout_fetch_ends) with the
         feed's "tail_values" (zeros unless config["bootstrap_truncated"] set some) (host copies; parity tests).
         Returns one stats dict per iteration."""
@@ -353,11 +374,11 @@ class TRPOAgent:
                               max_pathlength=cfg["max_steps"],
                               seed=rollout_seed(seed, i, self.rank),
                               train=self.train, **inj)                                   # :96-100
-            n_global = int(self._host_sum(n)[0])
+            n_global, row_offset = self._rank_rows(n)
             if self.continuous:
-                eng.rollout_gaussian_to_batch(n_global=n_global)
+                eng.rollout_gaussian_to_batch(n_global=n_global, row_offset=row_offset)
             else:
-                eng.rollout_to_batch(n_global=n_global)                                  # :108-122
+                eng.rollout_to_batch(n_global=n_global, row_offset=row_offset)           # :108-122
             have_base = self.vf.predict_engine(eng)                                      # :103
             if record:
                 rb = self.vf.net.predict(np.empty(n, np.float64)) if have_base else np.zeros(n)
@@ -400,6 +421,7 @@ class TRPOAgent:
                                              max_kl=cfg["max_kl"], compute_advantages=False))     # :144-158
                 if record:
                     rec["theta"] = eng.get_flat().copy()
+                    rec["theta_ls"] = eng.get_vector(VEC_THETA_LS).copy()   # the line search's point, before a revert
                     rec["vf_params"] = self.vf.net.get_params().copy()
                 numeptotal += int(ep_cnt)
                 exp = eng.explained_variance()                                           # :167

@@ -63,7 +63,14 @@ struct trpo_engine {
   // into the owner's captured update graph, and the owner's theta and CG scalar block (sc, fl), so the update's
   // statistics and step scaling read the CG's results where they always did; it owns every buffer with rows in it,
   // its weight images, its CG vectors and the scalar block of its own prepare pass's losses (loss_sc).
+  // The global mode (trpo_set_fvp_subsample_global) takes the stride over global row indices: the feed's first row
+  // has global index feed_row0, the Fisher rows are the local rows i with (feed_row0 + i) % k == 0, the first of them
+  // is fisher_phase(), and the child's n_global is ceil(n_global / k), which every rank knows without a collective.
+  // The child then also borrows its owner's transport (transport()): communicator, host callback and slots.
   int64_t fvp_stride = 1;
+  bool fvp_global = false;
+  int64_t row0_next = 0;   // trpo_set_row_offset: the global index of the next feeds' first row
+  int64_t feed_row0 = 0;   // ... and of the current feed's (recorded in every mode, read in the global one only)
   trpo_engine* fisher = nullptr;
   trpo_engine* owner = nullptr;
   std::string tag_prefix;   // of the child's profile tags ("sub."), in its owner's table
@@ -905,6 +912,7 @@ struct trpo_engine {
     REQUIRE(n_glob >= N, "n_global must be >= the rollout's steps");
     require_fisher_feed_ok(N, n_glob);
     use();
+    feed_row0 = row0_next;
     o.X = X;
     o.ldx = wp[0];
     o.head = old;
@@ -1006,6 +1014,10 @@ struct trpo_engine {
     HostArSlot* s = static_cast<HostArSlot*>(arg);
     if (s->e->host_ar(s->host, s->count, s->dtype, s->e->host_ar_ctx) != 0) s->e->har_failed = 1;
   }
+  // whose communicator, host callback and slots this engine's collectives use: a Fisher child's owner, so that the
+  // slot order of the host transport has one owner and the child's captured all-reduces keep their slots
+  trpo_engine* transport() { return owner ? owner : this; }
+  const trpo_engine* transport() const { return owner ? owner : this; }
   HostArSlot* har_slot(size_t bytes, int64_t count, int dtype) {
     if (har_next == har_slots.size()) {
       auto* s = new HostArSlot{this, nullptr, 0, 0, 0};
@@ -1037,11 +1049,12 @@ struct trpo_engine {
     }
   }
   void host_allreduce(void* buf, size_t bytes, size_t count, int dtype) {
-    HostArSlot* s = har_slot(bytes, (int64_t)count, dtype);
+    trpo_engine* t = transport();   // (a child's stream is its owner's)
+    HostArSlot* s = t->har_slot(bytes, (int64_t)count, dtype);
     HIPCHECK(hipMemcpyAsync(s->host, buf, bytes, hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipLaunchHostFunc(stream, host_ar_node, s));
     HIPCHECK(hipMemcpyAsync(buf, s->host, bytes, hipMemcpyHostToDevice, stream));
-    har_pending = true;
+    t->har_pending = true;
   }
   bool har_pending = false;     // a host node may still read its slot
   size_t har_graph_end = 0;     // slots [0, har_graph_end) belong to the captured update graph
@@ -1055,19 +1068,24 @@ struct trpo_engine {
     check_har();
     har_next = har_graph_end;
   }
-  bool multi_rank() const { return comm != nullptr || (host_ar && world > 1); }
+  bool multi_rank() const {   // a Fisher child answers for its owner
+    const trpo_engine* t = transport();
+    return t->comm != nullptr || (t->host_ar && t->world > 1);
+  }
   // RCCL when a communicator exists (any world size, world = 1 included: trpo_comm_init always
   // creates one), else the host transport for world > 1, else nothing to reduce
   void allreduce_f32(float* buf, size_t count) {
     if (!multi_rank()) return;
     Scope sp(this, "allreduce");
-    if (!comm) return host_allreduce(buf, count * sizeof(float), count, TRPO_F32);
-    NCCLCHECK(ncclAllReduce(buf, buf, count, ncclFloat32, ncclSum, comm, stream));
+    ncclComm_t cm = transport()->comm;
+    if (!cm) return host_allreduce(buf, count * sizeof(float), count, TRPO_F32);
+    NCCLCHECK(ncclAllReduce(buf, buf, count, ncclFloat32, ncclSum, cm, stream));
   }
   void allreduce_f64(double* buf, size_t count) {
     if (!multi_rank()) return;
-    if (!comm) return host_allreduce(buf, count * sizeof(double), count, TRPO_F64);
-    NCCLCHECK(ncclAllReduce(buf, buf, count, ncclFloat64, ncclSum, comm, stream));
+    ncclComm_t cm = transport()->comm;
+    if (!cm) return host_allreduce(buf, count * sizeof(double), count, TRPO_F64);
+    NCCLCHECK(ncclAllReduce(buf, buf, count, ncclFloat64, ncclSum, cm, stream));
   }
 
   // ------------------------------------------------------------------------
@@ -1335,33 +1353,55 @@ struct trpo_engine {
 
   // ---- Fisher subsampling ----
   static int64_t sub_rows(int64_t rows, int64_t k) { return (rows + k - 1) / k; }
-  // single-process only: the 1/N of a subsampled Fisher matrix over ranks would be sum_r ceil(n_r / k)
+  // the global mode's first Fisher row of a feed that starts at global row `first`, and its Fisher rows
+  static int64_t phase_of(int64_t first, int64_t k) { return (k - first % k) % k; }
+  int64_t fisher_phase() const { return fvp_global ? phase_of(feed_row0, fvp_stride) : 0; }
+  int64_t fisher_rows() const { return sub_rows(n - fisher_phase(), fvp_stride); }
+  // the global mode: the shard lies inside the global batch and holds a Fisher row (an engine needs n > 0, the child
+  // included)
+  void require_global_feed_ok(int64_t rows, int64_t rows_global, int64_t first, int64_t k) const {
+    if (first + rows > rows_global)
+      throw std::runtime_error("fvp_subsample (global rows): row offset " + std::to_string(first) + " + n = " +
+                               std::to_string(rows) + " exceeds n_global = " + std::to_string(rows_global));
+    if (rows <= phase_of(first, k))
+      throw std::runtime_error("fvp_subsample (global rows): the shard [" + std::to_string(first) + ", " +
+                               std::to_string(first + rows) + ") holds no multiple of the stride " + std::to_string(k) +
+                               ": a rank without a Fisher row is not supported");
+  }
+  // local mode, single-process only: the 1/N of a subsampled Fisher matrix over ranks would be sum_r ceil(n_r / k)
   void require_fisher_feed_ok(int64_t rows, int64_t rows_global) const {
+    if (fvp_global) return require_global_feed_ok(rows, rows_global, row0_next, fvp_stride);
     if (fvp_stride > 1 && rows_global != rows)
       throw std::runtime_error("fvp_subsample = " + std::to_string(fvp_stride) + " needs n_global == n (got n = " +
                                std::to_string(rows) + ", n_global = " + std::to_string(rows_global) +
                                "): multi-rank subsampling is not supported");
   }
   void require_single_rank_for_fisher(const char* call) const {
-    if (fvp_stride > 1)
+    if (fvp_stride > 1 && !fvp_global)
       throw std::runtime_error(std::string(call) + ": the engine has fvp_subsample = " + std::to_string(fvp_stride) +
                                ", which is single-process (set it back to 1 first)");
   }
-  void set_fvp_subsample(int64_t k) {
+  void set_fvp_subsample(int64_t k, bool global) {
     REQUIRE(!owner, "a Fisher sub-engine takes no stride of its own");
     if (k < 1) throw std::runtime_error("fvp_subsample: the stride must be >= 1, got " + std::to_string(k));
-    if (k > 1 && (comm || host_ar))
-      throw std::runtime_error(
-          "fvp_subsample > 1 is single-process: this engine has a communicator or a host all-reduce transport");
-    if (k > 1 && n > 0 && n_global != n)
-      throw std::runtime_error("fvp_subsample > 1 needs n_global == n: the current feed has n = " + std::to_string(n) +
-                               ", n_global = " + std::to_string(n_global));
-    if (k == fvp_stride) return;
+    if (k == 1) global = false;   // one mode at k = 1: every row
+    if (!global) {
+      if (k > 1 && (comm || host_ar))
+        throw std::runtime_error(
+            "fvp_subsample > 1 is single-process: this engine has a communicator or a host all-reduce transport");
+      if (k > 1 && n > 0 && n_global != n)
+        throw std::runtime_error("fvp_subsample > 1 needs n_global == n: the current feed has n = " +
+                                 std::to_string(n) + ", n_global = " + std::to_string(n_global));
+    } else if (n > 0) {
+      require_global_feed_ok(n, n_global, feed_row0, k);
+    }
+    if (k == fvp_stride && global == fvp_global) return;
     use();
     drop_graph();
     HIPCHECK(hipStreamSynchronize(stream));   // nothing enqueued still reads the old child's buffers
     drop_fisher();
     fvp_stride = 1;
+    fvp_global = false;
     cache.fisher_fed = cache.fisher_theta = false;
     if (k == 1) return;
     auto c = std::make_unique<trpo_engine>();
@@ -1374,12 +1414,13 @@ struct trpo_engine {
     c->prof = prof;
     fisher = c.release();
     fvp_stride = k;
+    fvp_global = global;
   }
-  // rows 0, k, 2k, ... of the feed into the child, one launch on the engine stream (capturable), then what a feed
-  // load runs after staging
+  // rows phase, phase + k, phase + 2k, ... of the feed into the child (phase = 0 in the local mode), one launch on the
+  // engine stream (capturable), then what a feed load runs after staging
   void gather_fisher_feed() {
     trpo_engine* c = fisher;
-    const int64_t ns = sub_rows(n, fvp_stride);
+    const int64_t ns = fisher_rows();
     GatherArgs ga{};
     auto wide = [&](const float* src, float* dst, int ld) { ga.wide[ga.nwide++] = GatherWide{src, dst, ld / 4, 0}; };
     wide(X, c->X, wp[0]);
@@ -1389,6 +1430,7 @@ struct trpo_engine {
     ga.scalar[ga.nscalar++] = GatherScalar{adv32, c->adv32};
     ga.n_sub = ns;
     ga.stride = fvp_stride;
+    ga.first = fisher_phase();
     if (gauss()) {
       ga.whole_src = logstd0;
       ga.whole_dst = c->logstd0;
@@ -1399,7 +1441,8 @@ struct trpo_engine {
       launch_gather_feed(ga, num_cus, stream);
       check_launch();
     }
-    c->n = c->n_global = ns;
+    c->n = ns;
+    c->n_global = fvp_global ? sub_rows(n_global, fvp_stride) : ns;
     c->update_x_amax();
     c->feed_loaded();
     cache.fisher_fed = true;
@@ -2215,6 +2258,7 @@ struct trpo_engine {
   struct GraphKey {
     int64_t n, n_global;
     int64_t fvp_stride;   // the Fisher child's rows follow from it: its launches are part of the graph
+    int64_t fvp_global, fisher_phase;   // ... and from the mode and the gather's first row
     const void* comm;   // the communicator / host transport the all-reduces were captured with
     const void* host_ar;
     int rank, world;
@@ -2228,7 +2272,7 @@ struct trpo_engine {
     Options opt;
   };
   static_assert(offsetof(GraphKey, opt) ==
-                    3 * sizeof(int64_t) + 2 * sizeof(void*) + 8 * sizeof(int) + 2 * sizeof(float) + 2 * sizeof(double),
+                    5 * sizeof(int64_t) + 2 * sizeof(void*) + 8 * sizeof(int) + 2 * sizeof(float) + 2 * sizeof(double),
                 "GraphKey is compared with memcmp: keep it free of padding");
   GraphKey graph_key(const trpo_update_params& prm) const {
     GraphKey k;
@@ -2236,6 +2280,8 @@ struct trpo_engine {
     k.n = n;
     k.n_global = n_global;
     k.fvp_stride = fvp_stride;
+    k.fvp_global = fvp_global ? 1 : 0;
+    k.fisher_phase = fisher_phase();
     k.comm = comm;
     k.host_ar = (const void*)host_ar;
     k.rank = rank;
@@ -2534,6 +2580,7 @@ int trpo_set_batch(trpo_engine* e, int64_t n, int64_t n_global, const float* sta
     e->use();
     e->n = n;
     e->n_global = n_global;
+    e->feed_row0 = e->row0_next;
     const int obs = e->w[0], A = e->w[e->L];
     // states -> [n][pad4(obs)], old_dist -> [n][pad4(A)] (padding zero)
     e->stage_rows(states, obs, e->wp[0], e->X, mem);
@@ -2566,6 +2613,7 @@ int trpo_set_batch_gaussian(trpo_engine* e, int64_t n, int64_t n_global, const f
     e->use();
     e->n = n;
     e->n_global = n_global;
+    e->feed_row0 = e->row0_next;
     const int A = e->w[e->L], ldA = e->wp[e->L];
     e->stage_rows(states, e->w[0], e->wp[0], e->X, mem);
     e->stage_rows(actions, A, ldA, e->actf, mem);
@@ -3143,7 +3191,34 @@ int trpo_rollout_gaussian_to_batch(trpo_engine* e, int64_t n_global) {
 int trpo_set_fvp_subsample(trpo_engine* e, int stride) {
   return guarded([&] {
     REQUIRE(e, "engine is NULL");
-    e->set_fvp_subsample(stride);
+    e->set_fvp_subsample(stride, false);
+  });
+}
+
+int trpo_set_fvp_subsample_global(trpo_engine* e, int stride) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    e->set_fvp_subsample(stride, true);
+  });
+}
+
+int trpo_set_row_offset(trpo_engine* e, int64_t row0) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    if (row0 < 0) throw std::runtime_error("trpo_set_row_offset: row0 must be >= 0, got " + std::to_string(row0));
+    e->row0_next = row0;
+  });
+}
+
+int trpo_get_fvp_subsample_global(trpo_engine* e, int* global, int64_t* n_sub_global, int64_t* phase,
+                                  int64_t* row0) {
+  return guarded([&] {
+    REQUIRE(e, "engine is NULL");
+    if (global) *global = e->fvp_global ? 1 : 0;
+    if (n_sub_global)
+      *n_sub_global = trpo_engine::sub_rows(e->fvp_global ? e->n_global : e->n, e->fvp_stride);
+    if (phase) *phase = e->fisher_phase();
+    if (row0) *row0 = e->row0_next;
   });
 }
 
@@ -3151,7 +3226,7 @@ int trpo_get_fvp_subsample(trpo_engine* e, int* stride, int64_t* n_sub) {
   return guarded([&] {
     REQUIRE(e, "engine is NULL");
     if (stride) *stride = (int)e->fvp_stride;
-    if (n_sub) *n_sub = trpo_engine::sub_rows(e->n, e->fvp_stride);
+    if (n_sub) *n_sub = e->n > 0 ? e->fisher_rows() : 0;
   });
 }
 

@@ -1,5 +1,7 @@
-// The Fisher feed's gather (trpo_set_fvp_subsample): rows 0, k, 2k, ... of the feed into the Fisher sub-engine's
-// buffers, device to device, every array in one launch.
+// The Fisher feed's gather (trpo_set_fvp_subsample[_global]): rows first, first + k, first + 2k, ... of the feed into
+// the Fisher sub-engine's buffers, device to device, every array in one launch.  `first` is 0 in the local mode and
+// the shard's phase (k - row0 % k) % k in the global one; rows are padded to 4 floats, so any first row is 16-byte
+// aligned in the wide arrays.
 //
 // The wide arrays (X, the old distribution / mean, a Gaussian engine's actions) have rows of q 16-byte units at a
 // 16-byte-aligned base (row widths are padded to 4 floats, hipMalloc aligns to 256 bytes): one lane moves one unit
@@ -25,15 +27,15 @@ __global__ __launch_bounds__(256) void gather_feed_kernel(GatherArgs a) {
     const GatherWide g = a.wide[s];
     const uint4* __restrict__ src = static_cast<const uint4*>(g.src);
     uint4* __restrict__ dst = static_cast<uint4*>(g.dst);
-    const int64_t q = g.q, total = a.n_sub * q, src_step = a.stride * q;
+    const int64_t q = g.q, total = a.n_sub * q, src_step = a.stride * q, src_first = a.first * q;
     for (int64_t u = tid; u < total; u += nthreads) {   // u = row * q + c: the guard of the last tile
       const int64_t row = u / q, c = u - row * q;
-      dst[u] = src[row * src_step + c];
+      dst[u] = src[src_first + row * src_step + c];
     }
   }
   const int64_t groups = (a.n_sub + 3) / 4;
   for (int s = 0; s < a.nscalar; ++s) {
-    const unsigned* __restrict__ src = static_cast<const unsigned*>(a.scalar[s].src);
+    const unsigned* __restrict__ src = static_cast<const unsigned*>(a.scalar[s].src) + a.first;
     unsigned* __restrict__ dst = static_cast<unsigned*>(a.scalar[s].dst);
     for (int64_t gi = tid; gi < groups; gi += nthreads) {
       const int64_t r0 = gi * 4;

@@ -388,11 +388,12 @@ struct GatherArgs {
   GatherScalar scalar[2];
   int nwide, nscalar;
   int64_t n_sub, stride;
+  int64_t first;            // the first source row (the global mode's phase; 0 in the local mode)
   const float* whole_src;   // copied whole (the old log-std vector), whole_n floats
   float* whole_dst;
   int64_t whole_n;
 };
-// grid sized from num_cus; the caller guarantees (n_sub - 1) * stride < the source's rows
+// grid sized from num_cus; the caller guarantees first + (n_sub - 1) * stride < the source's rows
 void launch_gather_feed(const GatherArgs& a, int num_cus, hipStream_t s);
 
 // ---------------------------------------------------------------------------

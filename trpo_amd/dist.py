@@ -29,6 +29,19 @@ def shard_bounds(n_total: int, world: int, starts: Optional[Sequence[int]] = Non
     return [(cuts[r], cuts[r + 1]) for r in range(world)]
 
 
+def fisher_rows(n: int, row_offset: int, k: int) -> Tuple[int, int]:
+    """The Fisher rows of a shard under ``fvp_subsample = k`` over global row indices: the shard holds rows
+    ``[row_offset, row_offset + n)`` of the global batch, its Fisher rows are the local rows ``i`` with
+    ``(row_offset + i) % k == 0``.  Returns ``(phase, n_sub)``: the first such local row and how many there are
+    (``n_sub = 0`` when the shard holds none).  Every rank knows ``N_sub = ceil(n_global / k)`` without a
+    collective; when the shards tile the batch their ``n_sub`` sum to it."""
+    n, row_offset, k = int(n), int(row_offset), int(k)
+    if k < 1 or n < 0 or row_offset < 0:
+        raise ValueError(f"fisher_rows needs k >= 1, n >= 0, row_offset >= 0 (got k={k}, n={n}, row_offset={row_offset})")
+    phase = (k - row_offset % k) % k
+    return phase, (-(-(n - phase) // k) if n > phase else 0)
+
+
 def init_engine_comm(engine, rank: int, world: int, group=None):
     """Create the engine's RCCL communicator: rank 0 draws the id, torch.distributed
     broadcasts it (any backend, e.g. gloo), every rank joins."""

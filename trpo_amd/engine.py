@@ -238,8 +238,11 @@ class Engine:
         return res
 
     # ------------------------------------------------------------------ feed
-    def set_batch(self, states, actions, advant, old_dist, n_global: Optional[int] = None):
+    def set_batch(self, states, actions, advant, old_dist, n_global: Optional[int] = None,
+                  row_offset: Optional[int] = None):
         n = int(states.shape[0])
+        if row_offset is not None:
+            self.set_row_offset(row_offset)
         n_global = n if n_global is None else int(n_global)
         s = _Arg(states, np.float32, (n, self.obs_dim))
         a = _Arg(actions, np.int64, (n,))
@@ -253,10 +256,13 @@ class Engine:
         self.n, self.n_global = n, n_global
         self._tail_ptr = None
 
-    def set_batch_gaussian(self, states, actions, advant, old_mean, old_logstd, n_global: Optional[int] = None):
+    def set_batch_gaussian(self, states, actions, advant, old_mean, old_logstd, n_global: Optional[int] = None,
+                           row_offset: Optional[int] = None):
         """The Gaussian engine's feed: states [n, obs_dim], actions [n, A], advant [n] (or None), old_mean [n, A]
         and old_logstd [A], float32; all host arrays or all device tensors."""
         n = int(states.shape[0])
+        if row_offset is not None:
+            self.set_row_offset(row_offset)
         n_global = n if n_global is None else int(n_global)
         A = self.n_actions
         s = _Arg(states, np.float32, (n, self.obs_dim))
@@ -389,18 +395,41 @@ class Engine:
         check(lib.trpo_fvp(self._h, vi.ptr, a.ptr, float(damping), vi.mem), "trpo_fvp")
         return res
 
-    def set_fvp_subsample(self, k: int):
+    def set_fvp_subsample(self, k: int, rows: str = "local"):
         """Evaluate every Fisher-vector product (fvp, cg, and the CG and shs products inside update) on rows
         0, k, 2k, ... of the feed, F_sub v + damping v; everything else stays on all rows.  k = 1 (the default)
-        is the plain engine.  Single-process only (include/trpo_engine.h)."""
-        check(lib.trpo_set_fvp_subsample(self._h, int(k)), "trpo_set_fvp_subsample")
+        is the plain engine.  rows="local" is single-process only; rows="global" takes the stride over global row
+        indices (set_row_offset, n_global) and works across ranks (include/trpo_engine.h)."""
+        if rows == "local":
+            check(lib.trpo_set_fvp_subsample(self._h, int(k)), "trpo_set_fvp_subsample")
+        elif rows == "global":
+            check(lib.trpo_set_fvp_subsample_global(self._h, int(k)), "trpo_set_fvp_subsample_global")
+        else:
+            raise ValueError(f"set_fvp_subsample: rows must be 'local' or 'global', got {rows!r}")
+
+    def set_row_offset(self, row0: int):
+        """The global index of the first row of the feeds that follow (default 0); read only by
+        set_fvp_subsample(k, rows="global")."""
+        check(lib.trpo_set_row_offset(self._h, int(row0)), "trpo_set_row_offset")
 
     @property
     def fvp_subsample(self):
-        """(k, n_sub): the stride in force and ceil(n / k) of the current feed."""
+        """(k, n_sub): the stride in force and this engine's Fisher rows of the current feed, ceil(n / k) in the
+        local mode."""
         k, ns = ctypes.c_int(0), ctypes.c_int64(0)
         check(lib.trpo_get_fvp_subsample(self._h, ctypes.byref(k), ctypes.byref(ns)), "trpo_get_fvp_subsample")
         return k.value, ns.value
+
+    @property
+    def fvp_subsample_global(self):
+        """(k, n_sub_r, N_sub, phase) in the global mode (trpo_amd.dist.fisher_rows), None in the local one."""
+        g, N, ph = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib.trpo_get_fvp_subsample_global(self._h, ctypes.byref(g), ctypes.byref(N), ctypes.byref(ph), None),
+              "trpo_get_fvp_subsample_global")
+        if not g.value:
+            return None
+        k, ns = self.fvp_subsample
+        return k, ns, N.value, ph.value
 
     def fvp_subsample_fetch(self) -> dict:
         """The Fisher feed as the engine holds it (host copies, unpadded): states, actions (int64 [n_sub], or
@@ -625,9 +654,11 @@ class Engine:
               "trpo_get_tail_values")
         return out
 
-    def rollout_to_batch(self, n_global: Optional[int] = None):
+    def rollout_to_batch(self, n_global: Optional[int] = None, row_offset: Optional[int] = None):
         """Load the rollout as the feed (states, actions, oldaction_dist, rewards, path starts) on the device."""
         N = self.rollout_steps
+        if row_offset is not None:
+            self.set_row_offset(row_offset)
         check(lib.trpo_rollout_to_batch(self._h, N if n_global is None else int(n_global)), "trpo_rollout_to_batch")
         self.n, self.n_global = N, (N if n_global is None else int(n_global))
         self._tail_ptr = None
@@ -674,10 +705,12 @@ class Engine:
         at float32(s_T) for cut-off paths, zeros otherwise), lengths, end_rows."""
         return self._fetch_ends("trpo_rollout_gaussian_fetch_ends", "final_means")
 
-    def rollout_gaussian_to_batch(self, n_global: Optional[int] = None):
+    def rollout_gaussian_to_batch(self, n_global: Optional[int] = None, row_offset: Optional[int] = None):
         """Load the Gaussian rollout as the feed (states, actions, old mean, the rollout's logstd, rewards, path
         starts) on the device."""
         N = getattr(self, "rollout_steps", None) or 0
+        if row_offset is not None:
+            self.set_row_offset(row_offset)
         ng = N if n_global is None else int(n_global)
         check(lib.trpo_rollout_gaussian_to_batch(self._h, ng), "trpo_rollout_gaussian_to_batch")
         self.n, self.n_global = N, ng
