@@ -498,6 +498,8 @@ typedef struct trpo_feed_view {
   const uint8_t* episode_starts;   /* [n] */
   const double* returns;     /* [n] f64 after the advantages of this feed were computed, else NULL */
   double* baseline;          /* [n] f64; trpo_set_baseline(e, view.baseline, TRPO_MEM_DEVICE) marks it set */
+  const int64_t* step_index; /* [n] each row's step index in its episode when the feed is a segment rollout's
+                              * (trpo_rollout_env_segment), else NULL: a path then starts at step 0 */
 } trpo_feed_view;
 int trpo_get_feed_view(trpo_engine* e, trpo_feed_view* out);
 /* The companion view of the feed's path ends, for the consumer that computes V(s_T) on the device (the
@@ -510,7 +512,8 @@ typedef struct trpo_tail_view {
   int obs_dim, n_actions;
   const float* final_obs32;  /* [n_paths][obs_dim] float32(s_T) */
   const float* final_dist;   /* [n_paths][n_actions] f32 */
-  const int64_t* lengths;    /* [n_paths] T */
+  const int64_t* lengths;    /* [n_paths] T, the episode's step count at s_T (of a segment rollout's path, which
+                              * may continue an episode: t0 + its rows, not the rows trpo_rollout_fetch_ends reports) */
   const uint8_t* truncated;  /* [n_paths] */
   const int64_t* end_rows;   /* [n_paths] */
   double* tail;              /* [n] f64, the engine's tail values */
@@ -612,6 +615,75 @@ int trpo_rollout_gaussian_to_batch(trpo_engine* e, int64_t n_global);
  * may be NULL.  Engine-free, current device. */
 int trpo_cont_env_step(int cenv, const double* state, const float* action, int64_t n, double* state_out,
                        double* obs_out, double* reward, uint8_t* done, int mem);
+
+/* ==== fixed-horizon rollout segments: environments that persist across calls ====================
+ * The rollouts above reset every environment at the start of every call and collect whole episodes.  A segment
+ * rollout collects as baselines' traj_segment_generator does: every environment takes exactly
+ * H = ceil(n_timesteps / n_envs) steps per call and continues where the previous call left it, so a rollout has
+ * exactly n_envs * H rows.  It runs on both heads and all five environments; observe, forward, sample and step are
+ * those of the whole-episode rollout, operation for operation.
+ *
+ * Per environment the engine keeps a carry, which outlives every rollout and trpo_set_flat: the state s
+ * [state_dim] f64, t (the steps taken in the current episode) and ret (the f64 sum of the current episode's rewards
+ * so far, added in step order).  With ep_max = min(max_pathlength, time_limit) one call runs, per environment:
+ *
+ *   resume ? load the carry : (reset with reset index 0; t = 0; ret = 0)
+ *   for k in 0 .. H-1:
+ *     row = env*H + k
+ *     observe, forward, sample, step, and record what the whole-episode rollout records per step, plus
+ *       step_index[row] = t              the step's index in its episode
+ *       starts[row] = (k == 0 || the previous step ended an episode)
+ *     t += 1; ret += reward
+ *     if done or t >= ep_max:
+ *       end record of kind 0 (terminated) or 1 (cut by the limit; a step that does both is a termination)
+ *       reset with the next reset index; t = 0; ret = 0
+ *   if the last step did not end an episode:
+ *     end record of kind 2 (cut by the segment); the environment is not reset
+ *   store the carry
+ *
+ * A path of a segment rollout is the fragment of an episode that lies in the call, so the paths tile the rows.
+ * An end record holds what the whole-episode rollout's does -- truncated (1 for kinds 1 and 2, so that both are
+ * bootstrapped from V(s_T)), the observation of s_T, the head row at float32(s_T) of a cut-off path from one more
+ * forward that draws nothing, the fragment's rows as `lengths` and its last row -- and four more fields: end_kind,
+ * t0 (the episode step index of the fragment's first row), the fragment's row count, and episode_return (ret at
+ * the path's end, earlier segments included).  For kind 2, s_T is the carried state: its observation is bitwise
+ * the next call's row-0 observation of that environment.
+ *
+ * Random draws are indexed per call: the action draw of the environment's step k is Philox (seed, env index,
+ * stream 0, k), or (Gaussian) the normal of component d at k*act_dim + d; reset draws are stream 1 at
+ * reset_index*reset_draws + i, reset_index counting this environment's resets within this call (resume = 0: the
+ * initial reset is index 0).  Injected action draws are [n_envs][H]([act_dim]); injected reset_uniforms are
+ * [n_envs][max_episodes_per_env][reset_draws] with max_episodes_per_env >= H + (resume ? 0 : 1).
+ *
+ * trpo_rollout_fetch*, trpo_rollout_gaussian_fetch*, *_fetch_ends, *_fetch_states and *_to_batch work on a segment
+ * rollout unchanged.  The feed loaded from one also carries step_index (trpo_feed_view.step_index), which the VF's
+ * time feature then uses in place of the distance to the path's start, and its trpo_tail_view.lengths are the
+ * episodes' step counts at s_T, t0 + rows.
+ *
+ * Refused with TRPO_ERR_STATE or TRPO_ERR_ARG, nothing launched, the previous rollout and the carry left as they
+ * were: resume = 1 without a carry, or with a carry of another environment, head or n_envs, or with a carried
+ * t >= ep_max (or < 0); the wrong head for the call; an engine whose obs_dim or head width is not the
+ * environment's; max_episodes_per_env too small for the injected resets.  n_envs * H rows beyond the engine's
+ * max_rows are refused by *_to_batch. */
+/* exactly H = ceil(p->n_timesteps / p->n_envs) steps per environment; resume = 0 resets every environment
+ * first, resume = 1 continues from the carry */
+int trpo_rollout_env_segment(trpo_engine* e, int env, const trpo_rollout_params* p, int resume, int64_t* n_steps_out,
+                             int64_t* n_paths_out);
+int trpo_rollout_gaussian_segment(trpo_engine* e, int cenv, const trpo_rollout_params* p, int resume,
+                                  int64_t* n_steps_out, int64_t* n_paths_out);
+/* of the last rollout when it was a segment rollout (TRPO_ERR_STATE otherwise); any may be NULL:
+ * end_kind [P] u8, t0 [P] i64, episode_returns [P] f64, step_index [N] i64 */
+int trpo_rollout_segment_fetch(trpo_engine* e, uint8_t* end_kind, int64_t* t0, double* episode_returns,
+                               int64_t* step_index, int mem);
+/* the carry: states [n_envs][state_dim] f64, t [n_envs] i64, returns [n_envs] f64; any output may be NULL.
+ * TRPO_ERR_STATE when there is none. */
+int trpo_rollout_carry_get(trpo_engine* e, int* env_out, int* n_envs_out, double* states, int64_t* t,
+                           double* returns, int mem);
+/* env: TRPO_ENV_* or TRPO_CENV_* by the engine's dist; the engine's obs_dim and head width must be the
+ * environment's (TRPO_ERR_ARG) */
+int trpo_rollout_carry_set(trpo_engine* e, int env, int n_envs, const double* states, const int64_t* t,
+                           const double* returns, int mem);
+int trpo_rollout_carry_clear(trpo_engine* e);
 
 /* ==== value-function baseline: class VF (utils.py:48-92) ==================================
  * Features [obs | action_dist | t/10] (VF._features, utils.py:70-77) -> fully_connected(64, relu)

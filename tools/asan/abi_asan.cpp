@@ -131,6 +131,14 @@ int main() {
   CHECK_ERR(trpo_rollout_gaussian_fetch_ends(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST),
             TRPO_ERR_ARG);
   CHECK_ERR(trpo_rollout_gaussian_to_batch(nullptr, 1), TRPO_ERR_ARG);
+  // the segment rollouts and their carry
+  CHECK_ERR(trpo_rollout_env_segment(nullptr, TRPO_ENV_CARTPOLE_V0, &rp, 0, nullptr, nullptr), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_gaussian_segment(nullptr, TRPO_CENV_PENDULUM_V1, &rp, 1, nullptr, nullptr), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_segment_fetch(nullptr, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_carry_get(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, TRPO_MEM_HOST), TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_carry_set(nullptr, TRPO_ENV_CARTPOLE_V0, 1, nullptr, nullptr, nullptr, TRPO_MEM_HOST),
+            TRPO_ERR_ARG);
+  CHECK_ERR(trpo_rollout_carry_clear(nullptr), TRPO_ERR_ARG);
   trpo_feed_view fv;
   CHECK_ERR(trpo_get_feed_view(nullptr, &fv), TRPO_ERR_ARG);
   double ev = 0.0;

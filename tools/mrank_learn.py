@@ -2,7 +2,7 @@
 
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29556 \
         tools/mrank_learn.py [--host-allreduce] [--iters 3] [--env NAME] [--gae LAMBDA] [--bootstrap]
-        [--fvp-subsample K]
+        [--fvp-subsample K] [--horizon T]
 
 --env NAME        any built-in environment (default CartPole-v0): the discrete ones of trpo_amd.engine.ENVS, or a
                   continuous one of CONT_ENVS, which makes the policy a diagonal Gaussian; the agent's dims are the
@@ -11,6 +11,9 @@
 --fvp-subsample K the Fisher-vector products on every K-th row by global row index
                   (config["fvp_subsample_rows"] = "global"); the one-rank reference then uses the local
                   set_fvp_subsample(K) on the concatenation
+--horizon T       fixed-horizon segments (config["segment_horizon"], needs --gae and --bootstrap): every rank holds
+                  exactly 4 * T rows per iteration, which is checked, and the mean reward is over the episodes that
+                  finished, by the ranks' rollout_segment_fetch records
 --host-allreduce  ranks share a GPU (RCCL refuses duplicate devices): the engine's and the VF's all-reduces
                   run through the stream-ordered host transport, summed by gloo
 Each rank rolls out its share of the timestep budget with its own draws (TRPOAgent.set_ranks). Checks:
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--gae", type=float, default=None)
     ap.add_argument("--bootstrap", action="store_true")
     ap.add_argument("--fvp-subsample", type=int, default=1)
+    ap.add_argument("--horizon", type=int, default=None)
     args = ap.parse_args()
 
     import torch
@@ -75,6 +79,8 @@ def main():
         cfg["bootstrap_truncated"] = True
     if K > 1:
         cfg.update(fvp_subsample=K, fvp_subsample_rows="global")
+    if args.horizon is not None:
+        cfg["segment_horizon"] = args.horizon
     agent = TRPOAgent(obs_dim, A, hidden=(64,), max_rows=8192, device=dev, config=cfg)
     agent.set_ranks(rank, world, host_allreduce=args.host_allreduce)
     hist = agent.learn(max_iterations=args.iters, n_envs=4, seed=5, log=None, record=True)
@@ -83,7 +89,8 @@ def main():
     roll_keys = ("obs", "actions", "means", "logstd", "rewards", "starts") if cont else (
         "obs", "actions", "action_dists", "rewards", "starts")
     mine = [{k: h[k] for k in keep if k in h} | {"rollout": {k: h["rollout"][k] for k in roll_keys},
-                                                 "tail_values": h["tail_values"]} for h in hist]
+                                                 "tail_values": h["tail_values"]} |
+            ({"segment": h["segment"]} if "segment" in h else {}) for h in hist]
     objs = [None] * world
     dist.all_gather_object(objs, mine)
     if rank == 0:
@@ -96,15 +103,28 @@ def main():
                 o = objs[r][i]
                 for k in ("reward_mean", "episodes", "k", "kl", "surr", "entropy", "explained_variance",
                           "reverted", "train"):
-                    assert o.get(k) == ref.get(k), (i, r, k, o.get(k), ref.get(k))
+                    same = o.get(k) == ref.get(k) or (k == "reward_mean" and o[k] != o[k] and ref[k] != ref[k])
+                    assert same, (i, r, k, o.get(k), ref.get(k))
                 for k in ("theta_before", "theta", "theta_ls", "vf_params"):
                     if k in ref:
                         assert np.array_equal(o[k], ref[k]), (i, r, k)
             ro = [objs[r][i]["rollout"] for r in range(world)]
             rewards = np.concatenate([x["rewards"] for x in ro])
             starts = np.concatenate([x["starts"] for x in ro]).astype(bool)
-            eps = np.add.reduceat(rewards, np.flatnonzero(starts))
-            assert abs(ref["reward_mean"] - eps.mean()) <= 1e-12 * abs(eps.mean()), (i, ref["reward_mean"], eps.mean())
+            if args.horizon is not None:
+                # equal row counts on every rank, and the mean over the episodes that finished in this iteration
+                rows = [objs[r][i]["steps"] for r in range(world)]
+                assert rows == [4 * args.horizon] * world, (i, rows)
+                sg = [objs[r][i]["segment"] for r in range(world)]
+                eps = np.concatenate([x["episode_returns"][x["end_kind"] < 2] for x in sg])
+                if len(eps) == 0:   # none finished: the previous value (NaN before the first)
+                    prev = objs[0][i - 1]["reward_mean"] if i else float("nan")
+                    assert ref["reward_mean"] == prev or (prev != prev and ref["reward_mean"] != ref["reward_mean"])
+            else:
+                eps = np.add.reduceat(rewards, np.flatnonzero(starts))
+            if len(eps):
+                assert abs(ref["reward_mean"] - eps.mean()) <= 1e-12 * abs(eps.mean()), (
+                    i, ref["reward_mean"], eps.mean())
             if ref.get("train"):
                 total_eps += len(eps)
                 assert ref["episodes"] == total_eps, (i, ref["episodes"], total_eps)
@@ -157,6 +177,8 @@ def main():
                   f"{float(at_ranks_point[('surr', 'kl', 'entropy').index(hk)])!r}")
             if not cont:
                 assert abs(st[k] - h0[hk]) <= 1e-5 * abs(st[k]) + 1e-9, (k, st[k], h0[hk])
+        if args.horizon is not None:
+            print(f"rows per rank and iteration: {[[objs[r][i]['steps'] for r in range(world)] for i in range(n_it)]}")
         print(f"{world} ranks x {n_it} learn() iterations: ranks bitwise identical; iteration 0 vs one rank: "
               f"theta rel L2 {r_th:.2e} (line-search point {r_ls:.2e}), k {st['k']}, rows {N}")
         print("MRANK LEARN OK")

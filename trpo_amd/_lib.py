@@ -70,7 +70,8 @@ class CommInfo(ctypes.Structure):
 class FeedView(ctypes.Structure):
     _fields_ = [("n", c_int64), ("n_global", c_int64), ("obs_dim", c_int), ("n_actions", c_int),
                 ("states", c_void_p), ("ld_states", c_int), ("old_dist", c_void_p), ("ld_old", c_int),
-                ("episode_starts", c_void_p), ("returns", c_void_p), ("baseline", c_void_p)]
+                ("episode_starts", c_void_p), ("returns", c_void_p), ("baseline", c_void_p),
+                ("step_index", c_void_p)]
 
 
 class TailView(ctypes.Structure):
@@ -171,6 +172,16 @@ SIGNATURES = {
     "trpo_rollout_gaussian_to_batch": (c_int, [c_void_p, c_int64]),
     "trpo_cont_env_step": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int]),
+    # fixed-horizon segment rollouts and their carry
+    "trpo_rollout_env_segment": (c_int, [c_void_p, c_int, POINTER(RolloutParams), c_int, POINTER(c_int64),
+                                         POINTER(c_int64)]),
+    "trpo_rollout_gaussian_segment": (c_int, [c_void_p, c_int, POINTER(RolloutParams), c_int, POINTER(c_int64),
+                                              POINTER(c_int64)]),
+    "trpo_rollout_segment_fetch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "trpo_rollout_carry_get": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_void_p,
+                                       c_int]),
+    "trpo_rollout_carry_set": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
+    "trpo_rollout_carry_clear": (c_int, [c_void_p]),
     # value-function baseline (utils.py:48-92)
     "trpo_vf_create": (c_int, [POINTER(c_void_p), c_int, POINTER(c_int), c_int, c_int64, c_int]),
     "trpo_vf_destroy": (None, [c_void_p]),

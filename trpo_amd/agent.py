@@ -58,6 +58,12 @@ CONFIG = {"max_steps": 1000, "episodes_per_roll": 1000, "gamma": 0.95, "cg_dampi
 # refusal, unless "fvp_subsample_rows": "global" (absent: "local") takes the stride over the rows' global indices
 # (Engine.set_fvp_subsample(k, rows="global"), trpo_amd.dist.fisher_rows): learn() then hands each rank's rollout
 # feed its row offset, and feed() / update() / update_stepwise() take one next to n_global.
+# "segment_horizon": T (absent: whole episodes) makes learn() collect as baselines' traj_segment_generator does
+# (Engine.rollout_segment): every environment takes exactly T steps per iteration and continues where the last
+# iteration left it, through the train = False tail of the loop too; a batch is n_envs * T rows on every rank.  It
+# needs "gae_lambda" and "bootstrap_truncated", which bootstrap the paths a segment cut from V(s_T).  The mean
+# episode reward is then over the episodes that finished in the iteration, with their whole returns; it keeps its
+# previous value when none did and is NaN before the first, so that no stop rule fires on it.
 DEFAULT_ENV = "CartPole-v0"
 REWARD_TARGET = 1.1 * 500   # trpo_inksci.py:135
 
@@ -182,6 +188,15 @@ class TRPOAgent:
         if self.bootstrap_truncated and self.config.get("gae_lambda") is None:
             raise ValueError("config['bootstrap_truncated'] needs config['gae_lambda']: the reference's "
                              "returns - baseline estimator takes no tail values")
+        self.segment_horizon = self.config.get("segment_horizon")
+        if self.segment_horizon is not None:
+            if int(self.segment_horizon) < 1:
+                raise ValueError("config['segment_horizon'] must be >= 1")
+            if self.config.get("gae_lambda") is None or not self.bootstrap_truncated:
+                raise ValueError("config['segment_horizon'] needs config['gae_lambda'] and "
+                                 "config['bootstrap_truncated']: without them a path the segment cut would be "
+                                 "scored as a termination")
+            self.segment_horizon = int(self.segment_horizon)
         self.env = self.config.get("env", DEFAULT_ENV)
         # a continuous-action environment (trpo_amd.engine.CONT_ENVS) makes the policy a diagonal Gaussian over
         # its act_dim action dimensions, which n_actions then counts; any other name is a discrete one's, as before
@@ -343,6 +358,11 @@ class TRPOAgent:
         point before a revert), rollout arrays, baselines, returns and
         standardised advantages, and how its paths ended ("ends", Engine.rollout_fetch_ends) with the
         feed's "tail_values" (zeros unless config["bootstrap_truncated"] set some) (host copies; parity tests).
+        With config["segment_horizon"] = T every iteration is a segment rollout of n_envs * T rows that resumes the
+        last one's environments (from a reset at iteration 0); draws(i)'s arrays are then those of
+        Engine.rollout_segment, "reward_mean" is over the episodes that finished in the iteration (NaN before the
+        first, the previous value when none did), "episodes" counts those, and record=True adds "segment"
+        (Engine.rollout_segment_fetch) and "carry" (Engine.rollout_carry).
         Returns one stats dict per iteration."""
         cfg = self.config
         eng = self.engine
@@ -354,6 +374,10 @@ class TRPOAgent:
         # worst case rows of one rollout: every environment overshoots its budget by one episode
         budget = -(-n_timesteps // n_envs)
         worst = n_envs * (budget + min(cfg["max_steps"], self.env_info["time_limit"]) - 1)
+        seg = self.segment_horizon        # None: whole episodes, as the reference collects
+        if seg is not None:
+            worst = n_envs * seg          # a segment rollout has exactly that many rows, on every rank
+            reward_mean = float("nan")    # until an episode has finished: no stop rule fires on it
         if worst > eng.max_rows:
             raise ValueError(f"learn(): a rollout of {n_envs} environments can reach {worst} steps, more than "
                              f"max_rows={eng.max_rows}; create the agent with max_rows >= {worst}")
@@ -369,12 +393,20 @@ class TRPOAgent:
                 ru, au, me = draws(i)
                 inj = {"reset_uniforms": ru, "action_normals" if self.continuous else "action_uniforms": au,
                        "max_episodes_per_env": me}
-            roll = eng.rollout_gaussian if self.continuous else eng.rollout
-            n, n_paths = roll(self.env, n_envs=n_envs, n_timesteps=n_timesteps,
-                              max_pathlength=cfg["max_steps"],
-                              seed=rollout_seed(seed, i, self.rank),
-                              train=self.train, **inj)                                   # :96-100
-            n_global, row_offset = self._rank_rows(n)
+            if seg is not None:
+                # every environment takes seg steps from where iteration i - 1 left it, train or not
+                roll = eng.rollout_gaussian_segment if self.continuous else eng.rollout_segment
+                n, n_paths = roll(self.env, n_envs=n_envs, horizon=seg, resume=i > 0,
+                                  max_pathlength=cfg["max_steps"], seed=rollout_seed(seed, i, self.rank),
+                                  train=self.train, **inj)
+                n_global, row_offset = n * self.world, n * self.rank   # equal row counts: nothing to gather
+            else:
+                roll = eng.rollout_gaussian if self.continuous else eng.rollout
+                n, n_paths = roll(self.env, n_envs=n_envs, n_timesteps=n_timesteps,
+                                  max_pathlength=cfg["max_steps"],
+                                  seed=rollout_seed(seed, i, self.rank),
+                                  train=self.train, **inj)                               # :96-100
+                n_global, row_offset = self._rank_rows(n)
             if self.continuous:
                 eng.rollout_gaussian_to_batch(n_global=n_global, row_offset=row_offset)
             else:
@@ -390,11 +422,20 @@ class TRPOAgent:
                 eng.compute_advantages_device(cfg["gamma"], returns_out=r_ret, advant_out=r_adv)
             else:
                 eng.compute_advantages_device(cfg["gamma"])                              # :104-117
-            ep = eng.rollout_fetch_stats()
-            episoderewards = np.add.reduceat(ep["rewards"], np.flatnonzero(ep["starts"]))   # :131
-            # the mean over every rank's episodes (one rank: episoderewards.mean())
-            ep_sum, ep_cnt = self._host_sum(episoderewards.sum(), len(episoderewards))
-            reward_mean = ep_sum / ep_cnt if self.world > 1 else float(episoderewards.mean())
+            if seg is not None:
+                # the episodes that finished in this segment (kinds 0 and 1), with their whole returns; an
+                # iteration in which none finished on any rank keeps the previous mean
+                sf = eng.rollout_segment_fetch()
+                episoderewards = sf["episode_returns"][sf["end_kind"] < 2]
+                ep_sum, ep_cnt = self._host_sum(episoderewards.sum(), len(episoderewards))
+                if ep_cnt > 0:
+                    reward_mean = ep_sum / ep_cnt if self.world > 1 else float(episoderewards.mean())
+            else:
+                ep = eng.rollout_fetch_stats()
+                episoderewards = np.add.reduceat(ep["rewards"], np.flatnonzero(ep["starts"]))   # :131
+                # the mean over every rank's episodes (one rank: episoderewards.mean())
+                ep_sum, ep_cnt = self._host_sum(episoderewards.sum(), len(episoderewards))
+                reward_mean = ep_sum / ep_cnt if self.world > 1 else float(episoderewards.mean())
             say("\n********** Iteration %i ************" % i)
             rec = {"iteration": i, "steps": n, "paths": n_paths, "train": self.train,
                    "reward_mean": float(reward_mean), "end_count": self.end_count}
@@ -403,6 +444,8 @@ class TRPOAgent:
                                      if self.continuous else (eng.rollout_fetch, eng.rollout_fetch_ends))
                 rec.update({"rollout": fetch(), "baseline": rb, "returns": r_ret, "advantages": r_adv,
                             "ends": fetch_ends(), "tail_values": r_tail})
+                if seg is not None:
+                    rec.update({"segment": sf, "carry": eng.rollout_carry()})
             if reward_mean > reward_target:                                              # :135-136
                 self.train = False
             rec["train"] = self.train                    # whether this iteration updates the policy

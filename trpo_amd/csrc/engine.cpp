@@ -358,11 +358,35 @@ struct trpo_engine {
     // [rows][A] f32 and the log-std vector [A] the rollout sampled with
     float* actf = nullptr;
     float* logstd = nullptr;
+    // a segment rollout's columns (allocated with the rest once a segment rollout asks): step_index [rows], the
+    // path regions' kind / t0 / episode return, and for the tail view the episode's step count at s_T
+    int64_t* step_index = nullptr;
+    uint8_t* end_kind = nullptr;
+    int64_t* end_t0 = nullptr;
+    double* end_ret = nullptr;
+    int64_t* cat_steps = nullptr;
   } roll;
   RolloutArgs roll_args{};   // the last rollout (roll_valid)
   int64_t roll_n = 0, roll_paths = 0, roll_maxcount = 0, roll_maxpaths = 0;
   bool roll_valid = false;
+  bool roll_segment = false;      // the last rollout was a segment rollout (seg_args holds roll_args and the rest)
+  SegmentArgs seg_args{};
   bool feed_is_rollout = false;   // the feed is the one trpo_rollout_to_batch loaded (trpo_get_tail_view)
+  // The segment rollouts' carry, apart from RollBufs: it outlives every rollout, whole-episode ones included, and
+  // trpo_set_flat.  Reallocated only when a carry of more environments or a wider state is stored.
+  struct Carry {
+    double* s = nullptr;       // [n_envs][state_dim]
+    int64_t* t = nullptr;
+    double* ret = nullptr;
+    int64_t cap = 0;           // doubles s holds
+    int cap_envs = 0;
+    bool valid = false;
+    bool continuous = false;
+    int env = 0, n_envs = 0, state_dim = 0;
+  } carry;
+  // the feed's step_index [cap] (a segment rollout's feed; trpo_feed_view.step_index), allocated on first use
+  int64_t* feed_step = nullptr;
+  bool feed_has_step = false;
 
   // profiling
   bool prof = false;
@@ -743,7 +767,7 @@ struct trpo_engine {
   // comes before anything of the previous rollout is freed or overwritten, so a refused call leaves it fetchable.
   // A Gaussian rollout copies the log-std vector aside first: it samples with the copy, and the feed built from it
   // (trpo_rollout_gaussian_to_batch) takes it as the old log-std whatever theta has become since.
-  void rollout(bool continuous, int env, const trpo_rollout_params& p) {
+  void rollout(bool continuous, int env, const trpo_rollout_params& p, bool segment = false, int resume = 0) {
     EnvDims ed{};
     REQUIRE(env_dims(continuous, env, &ed),
             std::string(continuous ? "unknown continuous environment id " : "unknown environment id ") +
@@ -758,18 +782,27 @@ struct trpo_engine {
     const int state_cap = ed.state_dim == ed.obs_dim ? 0 : ed.state_dim;   // such environments observe the state itself
     const int ep_max = std::min(p.max_pathlength, p.time_limit);
     const int64_t budget = (p.n_timesteps + p.n_envs - 1) / p.n_envs;
-    const int64_t env_cap = budget + ep_max - 1;
+    // a segment rollout writes exactly budget rows per environment: its regions are the concatenated rollout
+    const int64_t env_cap = segment ? budget : budget + ep_max - 1;
     const int64_t rows = env_cap * p.n_envs;
     REQUIRE(rows <= (int64_t(1) << 34), "rollout too large");
     const int64_t paths = budget * p.n_envs;   // every episode has at least one step
     if (p.reset_uniforms) {
       REQUIRE(p.max_episodes_per_env >= 1, "max_episodes_per_env required with reset_uniforms");
-      // every episode an environment can start must have its uniforms
-      REQUIRE((int64_t)p.max_episodes_per_env >= budget, "max_episodes_per_env must be >= ceil(n_timesteps/n_envs)");
+      // every episode an environment can start must have its uniforms; a segment resets after every step that
+      // ends an episode, its last included, and once more at the start unless it resumes
+      if (segment)
+        REQUIRE((int64_t)p.max_episodes_per_env >= budget + (resume ? 0 : 1),
+                "max_episodes_per_env must be >= ceil(n_timesteps/n_envs) + (resume ? 0 : 1)");
+      else
+        REQUIRE((int64_t)p.max_episodes_per_env >= budget, "max_episodes_per_env must be >= ceil(n_timesteps/n_envs)");
     }
+    if (segment && resume) carry_check(continuous, env, p.n_envs, ed.state_dim, ep_max);
+    if (segment) carry_reserve(p.n_envs, ed.state_dim);   // before the previous rollout is touched
     feed_is_rollout = false;   // the end records of the loaded feed and the regions are about to be overwritten
     roll_valid = false;
-    if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths || state_cap > roll.state_cap) {
+    if (rows > roll.rows || p.n_envs > roll.envs || paths > roll.paths || state_cap > roll.state_cap ||
+        (segment && !roll.step_index)) {
       for (void* ptr : roll.mem) HIPCHECK(hipFree(ptr));
       roll = RollBufs{};
       roll.rows = rows;
@@ -801,6 +834,13 @@ struct trpo_engine {
       roll.counts = ralloc<int64_t>(p.n_envs);
       roll.episodes = ralloc<int64_t>(p.n_envs);
       roll.offsets = ralloc<int64_t>((size_t)2 * p.n_envs);
+      if (segment) {
+        roll.step_index = ralloc<int64_t>(rows);
+        roll.end_kind = ralloc<uint8_t>(paths);
+        roll.end_t0 = ralloc<int64_t>(paths);
+        roll.end_ret = ralloc<double>(paths);
+        roll.cat_steps = ralloc<int64_t>(paths);
+      }
     }
     RolloutArgs a{};
     a.continuous = continuous;
@@ -850,10 +890,78 @@ struct trpo_engine {
     a.end_head = roll.end_dist;
     a.end_len = roll.end_len;
     a.end_row = roll.end_row;
-    launch_rollout(a, stream);
-    check_launch();
+    roll_segment = segment;
+    if (segment) {
+      SegmentArgs g{};
+      g.r = a;
+      g.resume = resume ? 1 : 0;
+      g.carry_s = carry.s;
+      g.carry_t = carry.t;
+      g.carry_ret = carry.ret;
+      g.step_index = roll.step_index;
+      g.end_kind = roll.end_kind;
+      g.end_t0 = roll.end_t0;
+      g.end_ret = roll.end_ret;
+      carry.valid = false;   // until the kernel that rewrites it is enqueued
+      launch_rollout_segment(g, stream);
+      check_launch();
+      carry.valid = true;
+      carry.continuous = continuous;
+      carry.env = env;
+      carry.n_envs = p.n_envs;
+      carry.state_dim = ed.state_dim;
+      seg_args = g;
+    } else {
+      launch_rollout(a, stream);
+      check_launch();
+    }
     roll_args = a;
     rollout_offsets(p.n_envs);
+  }
+
+  // room for a carry of n_envs environments; a valid carry survives (it is only ever grown by the call that
+  // replaces it, and a resumed rollout has checked that it fits already)
+  void carry_reserve(int n_envs, int state_dim) {
+    const int64_t need = (int64_t)n_envs * state_dim;
+    if (need <= carry.cap && n_envs <= carry.cap_envs) return;
+    double* s = nullptr;
+    int64_t* t = nullptr;
+    double* ret = nullptr;
+    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&s), (size_t)need * sizeof(double)));
+    if (hipMalloc(reinterpret_cast<void**>(&t), (size_t)n_envs * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&ret), (size_t)n_envs * sizeof(double)) != hipSuccess) {
+      (void)hipFree(s);
+      (void)hipFree(t);
+      throw ::trpo_abi::HipError("hipMalloc of the rollout carry failed");
+    }
+    HIPCHECK(hipStreamSynchronize(stream));   // nothing enqueued reads the old buffers past this point
+    carry_free();
+    carry.s = s;
+    carry.t = t;
+    carry.ret = ret;
+    carry.cap = need;
+    carry.cap_envs = n_envs;
+  }
+  void carry_free() {
+    (void)hipFree(carry.s);
+    (void)hipFree(carry.t);
+    (void)hipFree(carry.ret);
+    carry = Carry{};
+  }
+  // resume = 1: the carry must be this environment's, under this head, of as many environments, and every carried
+  // episode must have a step left
+  void carry_check(bool continuous, int env, int n_envs, int state_dim, int ep_max) {
+    if (!carry.valid)
+      throw std::runtime_error("resume = 1 needs a carry: no segment rollout or trpo_rollout_carry_set came before");
+    if (carry.continuous != continuous || carry.env != env || carry.n_envs != n_envs || carry.state_dim != state_dim)
+      throw std::runtime_error("resume = 1: the carry is of environment id " + std::to_string(carry.env) +
+                               (carry.continuous ? " (continuous)" : " (discrete)") + " with n_envs " +
+                               std::to_string(carry.n_envs) + ", not of this call's");
+    std::vector<int64_t> t(n_envs);
+    copy_out(t.data(), carry.t, t.size() * sizeof(int64_t), TRPO_MEM_HOST);
+    for (int i = 0; i < n_envs; ++i)
+      REQUIRE(t[i] >= 0 && t[i] < ep_max, "resume = 1: environment " + std::to_string(i) + " carries t = " +
+                                              std::to_string(t[i]) + ", outside [0, min(max_pathlength, time_limit))");
   }
 
   // after a rollout kernel: row offsets [n_envs], then path offsets [n_envs] (one upload), and the totals
@@ -882,6 +990,12 @@ struct trpo_engine {
   void rollout_compact(const RolloutOut& o) {
     REQUIRE(roll_valid, "no rollout to fetch");
     launch_rollout_compact(roll_args, roll.offsets, o, o.ends_only ? roll_maxpaths : roll_maxcount, stream);
+    check_launch();
+  }
+
+  void segment_compact(const SegmentOut& o) {
+    if (!(roll_valid && roll_segment)) throw std::runtime_error("the last rollout was not a segment rollout");
+    launch_rollout_segment_compact(seg_args, roll.path_offsets, o, roll_maxpaths, stream);
     check_launch();
   }
 
@@ -927,12 +1041,21 @@ struct trpo_engine {
     o.end_len = roll.cat_len;
     o.end_rows = roll.cat_rows;
     rollout_compact(o);
+    if (roll_segment) {
+      // the feed's step_index, and per path the episode's step count at s_T for the tail features' time entry
+      if (!feed_step) feed_step = dalloc<int64_t>(cap);
+      SegmentOut so{};
+      so.step_index = feed_step;
+      so.end_steps = roll.cat_steps;
+      segment_compact(so);
+    }
     if (gauss()) copy_in(logstd0, roll.logstd, (size_t)w[L] * sizeof(float), TRPO_MEM_DEVICE);
     n = N;
     n_global = n_glob;
     update_x_amax();
     feed_loaded();
     feed_is_rollout = true;
+    feed_has_step = roll_segment;
     have_rewards = true;
     have_baseline = false;
     HIPCHECK(hipStreamSynchronize(stream));
@@ -958,6 +1081,7 @@ struct trpo_engine {
     allocs.clear();
     for (void* ptr : roll.mem) (void)hipFree(ptr);
     roll.mem.clear();
+    carry_free();
     drop_graph();
     free_har_slots();
     if (hsc) (void)hipHostFree(hsc);
@@ -1335,6 +1459,7 @@ struct trpo_engine {
     have_rewards = false;
     have_tail = false;
     feed_is_rollout = false;
+    feed_has_step = false;
   }
 
   void update_x_amax() {
@@ -2639,6 +2764,7 @@ int trpo_set_rewards(trpo_engine* e, const double* rewards, const uint8_t* start
     e->cache.rewards_changed();
     e->have_tail = false;
     e->feed_is_rollout = false;
+    e->feed_has_step = false;   // the new path starts are not the segment's
   });
 }
 
@@ -3022,6 +3148,7 @@ int trpo_get_feed_view(trpo_engine* e, trpo_feed_view* v) {
     v->episode_starts = e->have_rewards ? e->starts : nullptr;
     v->returns = e->cache.have_returns ? e->returns : nullptr;   // stale until the advantages are computed
     v->baseline = e->baseline;
+    v->step_index = e->have_rewards && e->feed_has_step ? e->feed_step : nullptr;
   });
 }
 
@@ -3051,7 +3178,8 @@ int trpo_get_tail_view(trpo_engine* e, trpo_tail_view* v) {
     v->n_actions = e->w[e->L];
     v->final_obs32 = e->roll.cat_obs32;
     v->final_dist = e->roll.cat_dist;
-    v->lengths = e->roll.cat_len;
+    // the time entry of s_T's features is the episode's step count there: of a segment's fragment, t0 + rows
+    v->lengths = e->roll_segment ? e->roll.cat_steps : e->roll.cat_len;
     v->truncated = e->roll.cat_truncated;
     v->end_rows = e->roll.cat_rows;
     v->tail = e->tail;
@@ -3185,6 +3313,103 @@ int trpo_rollout_gaussian_to_batch(trpo_engine* e, int64_t n_global) {
     o.actf = e->actf;
     o.ld_actf = e->wp[e->L];
     e->rollout_to_feed(o, n_global);
+  });
+}
+
+// ---- fixed-horizon segment rollouts: environments that persist across calls ---------------------------------
+int trpo_rollout_env_segment(trpo_engine* e, int env, const trpo_rollout_params* p, int resume, int64_t* n_steps_out,
+                             int64_t* n_paths_out) {
+  return guarded([&] {
+    REQUIRE(e && p, "NULL argument");
+    REQUIRE(resume == 0 || resume == 1, "resume must be 0 or 1");
+    e->require_dist(TRPO_DIST_CATEGORICAL, "trpo_rollout_env_segment");
+    e->use();
+    e->rollout(false, env, *p, true, resume);
+    if (n_steps_out) *n_steps_out = e->roll_n;
+    if (n_paths_out) *n_paths_out = e->roll_paths;
+  });
+}
+
+int trpo_rollout_gaussian_segment(trpo_engine* e, int cenv, const trpo_rollout_params* p, int resume,
+                                  int64_t* n_steps_out, int64_t* n_paths_out) {
+  return guarded([&] {
+    REQUIRE(e && p, "NULL argument");
+    REQUIRE(resume == 0 || resume == 1, "resume must be 0 or 1");
+    e->require_dist(TRPO_DIST_GAUSSIAN, "trpo_rollout_gaussian_segment");
+    REQUIRE(e->w[e->L] <= 64, "rollout_gaussian_segment: act_dim must be <= 64 (one wave per environment)");
+    e->use();
+    e->rollout(true, cenv, *p, true, resume);
+    if (n_steps_out) *n_steps_out = e->roll_n;
+    if (n_paths_out) *n_paths_out = e->roll_paths;
+  });
+}
+
+int trpo_rollout_segment_fetch(trpo_engine* e, uint8_t* end_kind, int64_t* t0, double* episode_returns,
+                               int64_t* step_index, int mem) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    if (!e->roll_valid) throw std::runtime_error("no rollout to fetch");
+    if (!e->roll_segment) throw std::runtime_error("the last rollout was not a segment rollout");
+    e->use();
+    const size_t P = (size_t)e->roll_paths, N = (size_t)e->roll_n;
+    SegmentOut o{};
+    Staging st(mem, e->stream);
+    o.end_kind = st.out(end_kind, P);
+    o.end_t0 = st.out(t0, P);
+    o.end_ret = st.out(episode_returns, P);
+    o.step_index = st.out(step_index, N);
+    e->segment_compact(o);
+    st.fetch();
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int trpo_rollout_carry_get(trpo_engine* e, int* env_out, int* n_envs_out, double* states, int64_t* t, double* returns,
+                           int mem) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    if (!e->carry.valid) throw std::runtime_error("there is no rollout carry");
+    e->use();
+    const auto& c = e->carry;
+    if (env_out) *env_out = c.env;
+    if (n_envs_out) *n_envs_out = c.n_envs;
+    if (states) e->copy_out(states, c.s, (size_t)c.n_envs * c.state_dim * sizeof(double), mem);
+    if (t) e->copy_out(t, c.t, (size_t)c.n_envs * sizeof(int64_t), mem);
+    if (returns) e->copy_out(returns, c.ret, (size_t)c.n_envs * sizeof(double), mem);
+    HIPCHECK(hipStreamSynchronize(e->stream));
+  });
+}
+
+int trpo_rollout_carry_set(trpo_engine* e, int env, int n_envs, const double* states, const int64_t* t,
+                           const double* returns, int mem) {
+  return guarded([&] {
+    REQUIRE(e && states && t && returns, "NULL argument");
+    EnvDims ed{};
+    REQUIRE(env_dims(e->gauss(), env, &ed),
+            std::string(e->gauss() ? "unknown continuous environment id " : "unknown environment id ") +
+                std::to_string(env));
+    REQUIRE(n_envs >= 1 && n_envs <= (1 << 20), "n_envs out of range");
+    REQUIRE(e->w[0] == ed.obs_dim && e->w[e->L] == ed.head_dim,
+            std::string(ed.name) + " does not fit this engine's obs_dim and head width");
+    e->use();
+    e->carry_reserve(n_envs, ed.state_dim);
+    e->carry.valid = false;
+    e->copy_in(e->carry.s, states, (size_t)n_envs * ed.state_dim * sizeof(double), mem);
+    e->copy_in(e->carry.t, t, (size_t)n_envs * sizeof(int64_t), mem);
+    e->copy_in(e->carry.ret, returns, (size_t)n_envs * sizeof(double), mem);
+    HIPCHECK(hipStreamSynchronize(e->stream));
+    e->carry.valid = true;
+    e->carry.continuous = e->gauss();
+    e->carry.env = env;
+    e->carry.n_envs = n_envs;
+    e->carry.state_dim = ed.state_dim;
+  });
+}
+
+int trpo_rollout_carry_clear(trpo_engine* e) {
+  return guarded([&] {
+    REQUIRE(e, "NULL argument");
+    e->carry.valid = false;
   });
 }
 

@@ -757,10 +757,11 @@ namespace trpo {
 // ---------------------------------------------------------------------------
 size_t vf_pos_workspace_bytes(int64_t n);
 // feat [n][Fp] = [obs | dist | f32(t/10)] with t the step index within each path
-// (starts[r] = 1 opens a path; starts may be NULL: one path); lastpos [n] scratch
+// (starts[r] = 1 opens a path; starts may be NULL: one path); lastpos [n] scratch.  step_index [n], when given, is t
+// itself (a segment rollout's feed, whose first path may continue an episode) and starts is not read.
 void launch_vf_features(const float* obs, int obs_dim, int ld_obs, const float* dist, int A, int ld_dist,
                         const uint8_t* starts, int64_t n, int64_t* lastpos, void* ws, float* feat, int Fp,
-                        hipStream_t s);
+                        hipStream_t s, const int64_t* step_index = nullptr);
 // feat [n_paths][Fp] = [final_obs | final_dist | f32(T/10)]: the features of s_T, the state after a path's
 // T steps (row t = T of launch_vf_features)
 void launch_vf_tail_features(const float* obs, int obs_dim, const float* dist, int A, const int64_t* lengths,
@@ -875,8 +876,36 @@ struct RolloutOut {         // concatenated outputs; any pointer may be NULL
   int64_t* end_len;
   int64_t* end_rows;        // index of the path's last step in the concatenated rollout
 };
+// The fixed-horizon segment rollout (rollout_segment_kernel; include/trpo_engine.h has its definition): every
+// environment takes exactly r.budget steps (r.env_cap == r.budget, so row = env * budget + k and the regions are
+// already concatenated) and continues from the carry.  It has arguments of its own, so that RolloutArgs and with it
+// the whole-episode kernels stay what they are.
+struct SegmentArgs {
+  RolloutArgs r;            // r.end_len holds a fragment's row count, r.max_episodes >= budget + (resume ? 0 : 1)
+  int resume;               // 1: start from the carry; 0: reset every environment first (reset index 0)
+  // the carry, per environment; read when resume, always written
+  double* carry_s;          // [n_envs][state_dim]
+  int64_t* carry_t;         // steps taken in the current episode
+  double* carry_ret;        // the current episode's rewards so far, summed in step order
+  int64_t* step_index;      // [n_envs * budget] the step's index in its episode
+  // per-environment path regions, beside r.end_*
+  uint8_t* end_kind;        // 0 terminated, 1 cut by time_limit / max_pathlength, 2 cut by the segment
+  int64_t* end_t0;          // the episode step index of the fragment's first row
+  double* end_ret;          // the episode's return at the path's end, earlier segments included
+};
+struct SegmentOut {         // concatenated; any pointer may be NULL
+  uint8_t* end_kind;        // [n_paths]
+  int64_t* end_t0;
+  double* end_ret;
+  int64_t* end_steps;       // end_t0 + the fragment's rows: the episode's step count at s_T
+  int64_t* step_index;      // [n_envs * budget]
+};
 size_t rollout_lds_bytes(int maxw);
 void launch_rollout(const RolloutArgs& a, hipStream_t s);
+void launch_rollout_segment(const SegmentArgs& g, hipStream_t s);
+// path_offsets as RolloutOut's; max_paths = the largest episode count of one environment
+void launch_rollout_segment_compact(const SegmentArgs& g, const int64_t* path_offsets, const SegmentOut& o,
+                                    int64_t max_paths, hipStream_t s);
 void launch_rollout_compact(const RolloutArgs& a, const int64_t* offsets, const RolloutOut& o, int64_t max_count,
                             hipStream_t s);
 void launch_act(const PolicyShape& ps, const float* theta, int maxw, const float* states, int64_t n, const double* r,

@@ -46,6 +46,11 @@
 // compaction kernel concatenates these records too, so that GAE can bootstrap the
 // cut-off paths from V(s_T) (vf.hip: the VF's features are [obs | dist | t/10]).
 // The per-step outputs and the Philox draw indices do not depend on any of it.
+//
+// rollout_segment_kernel collects the other way, as baselines' traj_segment_generator does: every environment
+// takes exactly ceil(n_timesteps / n_envs) steps per call and continues, from a per-environment carry (state,
+// episode step count, episode return so far), where the previous call left it.  Its paths are the fragments of
+// episodes that lie in the segment; a fragment the segment cut is a cut-off path whose s_T is the carried state.
 #include "common.h"
 #include "kernels.h"
 
@@ -535,6 +540,166 @@ __global__ void __launch_bounds__(kRollWaves * 64) rollout_kernel(const RolloutA
   }
 }
 
+// The fixed-horizon segment rollout: every environment takes exactly a.budget steps and continues where the carry
+// says the previous call left it (include/trpo_engine.h, trpo_rollout_env_segment, is the definition).  The step is
+// rollout_kernel's, line for line; what differs is the bookkeeping around it: an episode's step index t and return
+// live across calls, a path is the fragment of an episode that lies in this segment, and an environment is reset
+// only after a step that ended its episode, the segment's last step included.  Draw k of the call is the action
+// draw of the environment's step k; reset draws count this environment's resets within the call.  A kernel of
+// its own rather than a flag of rollout_kernel, whose five instantiations stay what they were.
+template <class Env>
+__global__ void __launch_bounds__(kRollWaves * 64) rollout_segment_kernel(const SegmentArgs g) {
+  extern __shared__ float lds[];
+  const RolloutArgs& a = g.r;
+  constexpr int kS = Env::kState, obs_dim = Env::kObs, A = Env::kHead;   // the engine checked ps against them
+  constexpr bool kCont = Env::kContinuous;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int env = blockIdx.x * kRollWaves + wv;
+  if (env >= a.n_envs) return;
+  float* buf0 = lds + (size_t)wv * 2 * a.maxw;
+  float* buf1 = buf0 + a.maxw;
+  const int64_t H = a.budget, base = (int64_t)env * H;
+  const int ep_max = a.max_pathlength < a.time_limit ? a.max_pathlength : a.time_limit;
+  double s[kS];
+  int64_t t = 0;       // steps taken in the current episode
+  double ret = 0.0;    // its rewards so far
+  int resets = 0;      // this environment's resets within this call
+  auto reset = [&]() {
+    double u[Env::kResetDraws];
+#pragma unroll
+    for (int i = 0; i < Env::kResetDraws; ++i)
+      u[i] = a.reset_u ? a.reset_u[((int64_t)env * a.max_episodes + resets) * Env::kResetDraws + i]
+                       : uniform53(a.seed, (uint32_t)env, 1u, (uint64_t)resets * Env::kResetDraws + i);
+    Env::reset(s, u);
+    ++resets;
+    t = 0;
+    ret = 0.0;
+  };
+  if (g.resume) {
+#pragma unroll
+    for (int i = 0; i < kS; ++i) s[i] = g.carry_s[(int64_t)env * kS + i];
+    t = g.carry_t[env];
+    ret = g.carry_ret[env];
+  } else {
+    reset();
+  }
+  int paths = 0;         // end records written
+  int64_t frag0 = 0;     // the current fragment's first step of this call
+  int64_t t0 = t;        // and that step's index in its episode
+  bool fresh = true;     // the next row opens a path
+  for (int64_t k = 0; k < H; ++k) {
+    const int64_t row = base + k;
+    // act(ob): the obs fed to the float32 state placeholder, recorded as the float64 ob
+    if (lane < obs_dim) {
+      const double ob = Env::observe(s, lane);
+      buf0[lane] = (float)ob;
+      a.obs[row * obs_dim + lane] = ob;
+    }
+    if constexpr (!Env::kObsIsState) {
+      if (lane < kS) a.env_state[row * kS + lane] = s[lane];
+    }
+    wave_sync();
+    const float h = wave_head<kCont>(a.ps, a.theta, buf0, buf1, A, lane);
+    double reward;
+    bool done;
+    if constexpr (kCont) {
+      float act[A];
+#pragma unroll
+      for (int d = 0; d < A; ++d) {
+        const float m = wave_bcast(h, d);
+        double xi = 0.0;
+        if (a.train) xi = a.draws ? a.draws[row * A + d] : normal53(a.seed, (uint32_t)env, 0u, (uint64_t)k * A + d);
+        act[d] = a.train ? gauss_act(m, a.logstd[d], xi) : m;
+        if (lane == d) {
+          a.actf[row * A + d] = act[d];
+          a.head[row * A + d] = m;
+          a.noise[row * A + d] = xi;
+        }
+      }
+      done = Env::step(s, act, reward);
+    } else {
+      if (lane < A) a.head[row * A + lane] = h;
+      const double r = a.draws ? a.draws[row] : uniform53(a.seed, (uint32_t)env, 0u, (uint64_t)k);
+      const int action = wave_choose(h, A, r, a.train);
+      done = Env::step(s, action, reward);
+      if (lane == 0) {
+        a.acti[row] = action;
+        a.noise[row] = r;
+      }
+    }
+    // step_index goes with the group of stores rollout_kernel has here (one wait for the group's pointers)
+    if (lane == 0) {
+      a.rewards[row] = reward;
+      a.starts[row] = fresh ? 1 : 0;
+      g.step_index[row] = t;
+    }
+    t += 1;
+    ret = ret + reward;
+    // the TimeLimit wrapper and max_pathlength end an episode at its step ep_max; a termination there wins
+    const bool ended = done || t >= ep_max;
+    fresh = ended;
+    wave_sync();
+    if (!ended && k + 1 < H) continue;
+    // The fragment's end record, as rollout_kernel writes a path's: s is s_T, and a cut-off path -- by the limit
+    // (kind 1) or by the segment (kind 2), whose s_T is the carried state -- records the head row there from one
+    // more forward that draws nothing.
+    const int64_t path = base + paths;   // at most one record per step: paths <= H
+    const bool truncated = !done;
+    const double obT = lane < obs_dim ? Env::observe(s, lane) : 0.0;
+    float hT = 0.0f;
+    if (truncated) {
+      if (lane < obs_dim) buf0[lane] = (float)obT;
+      wave_sync();
+      hT = wave_head<kCont>(a.ps, a.theta, buf0, buf1, A, lane);
+      wave_sync();
+    }
+    if (lane < obs_dim) a.end_obs[path * obs_dim + lane] = obT;
+    if (lane < A) a.end_head[path * A + lane] = hT;
+    if (lane == 0) {
+      a.end_truncated[path] = truncated ? 1 : 0;
+      a.end_len[path] = k + 1 - frag0;
+      a.end_row[path] = k;
+      g.end_kind[path] = done ? 0 : (ended ? 1 : 2);
+      g.end_t0[path] = t0;
+      g.end_ret[path] = ret;
+    }
+    ++paths;
+    if (ended) {
+      reset();
+      frag0 = k + 1;
+      t0 = 0;
+    }
+  }
+  if (lane < kS) g.carry_s[(int64_t)env * kS + lane] = s[lane];
+  if (lane == 0) {
+    g.carry_t[env] = t;
+    g.carry_ret[env] = ret;
+    a.counts[env] = H;
+    a.episodes[env] = paths;
+  }
+}
+
+// the segment rollout's per-path columns, concatenated like rollout_compact_kernel's end records; its rows need no
+// move (every environment has exactly budget of them), step_index is copied out as it lies
+__global__ void __launch_bounds__(256) rollout_segment_compact_kernel(const SegmentArgs g, const int64_t* path_offsets,
+                                                                      SegmentOut o) {
+  const RolloutArgs& a = g.r;
+  const int env = blockIdx.y;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o.step_index) {
+    const int64_t r0 = (int64_t)env * a.budget;
+    for (int64_t i = i0; i < a.budget; i += stride) o.step_index[r0 + i] = g.step_index[r0 + i];
+  }
+  const int64_t np = a.episodes[env], pdst0 = path_offsets[env], psrc0 = (int64_t)env * a.budget;
+  for (int64_t i = i0; i < np; i += stride) {
+    const int64_t s = psrc0 + i, d = pdst0 + i;
+    if (o.end_kind) o.end_kind[d] = g.end_kind[s];
+    if (o.end_t0) o.end_t0[d] = g.end_t0[s];
+    if (o.end_ret) o.end_ret[d] = g.end_ret[s];
+    if (o.end_steps) o.end_steps[d] = g.end_t0[s] + a.end_len[s];
+  }
+}
+
 // concatenate the per-environment regions in environment order
 __global__ void __launch_bounds__(256) rollout_compact_kernel(const RolloutArgs a, const int64_t* offsets,
                                                               RolloutOut o) {
@@ -697,6 +862,24 @@ void launch_rollout(const RolloutArgs& a, hipStream_t s) {
                        rollout_lds_bytes(a.maxw), s, a);
   });
   if (!known) throw std::invalid_argument("launch_rollout: unknown environment id");
+}
+
+void launch_rollout_segment(const SegmentArgs& g, hipStream_t s) {
+  const RolloutArgs& a = g.r;
+  if (a.env_cap != a.budget) throw std::invalid_argument("launch_rollout_segment: env_cap must be the budget");
+  const unsigned blocks = (unsigned)((a.n_envs + kRollWaves - 1) / kRollWaves);
+  const bool known = with_any_env(a.continuous, a.env, [&](auto e) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rollout_segment_kernel<decltype(e)>), dim3(blocks), dim3(kRollWaves * 64),
+                       rollout_lds_bytes(a.maxw), s, g);
+  });
+  if (!known) throw std::invalid_argument("launch_rollout_segment: unknown environment id");
+}
+
+void launch_rollout_segment_compact(const SegmentArgs& g, const int64_t* path_offsets, const SegmentOut& o,
+                                    int64_t max_paths, hipStream_t s) {
+  const int64_t most = o.step_index ? g.r.budget : max_paths;
+  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((most + 255) / 256, 64));
+  hipLaunchKernelGGL(rollout_segment_compact_kernel, dim3(bx, g.r.n_envs), dim3(256), 0, s, g, path_offsets, o);
 }
 
 void launch_rollout_compact(const RolloutArgs& a, const int64_t* offsets, const RolloutOut& o, int64_t max_count,

@@ -392,7 +392,7 @@ int trpo_vf_set_features_view(trpo_vf* e, const trpo_feed_view* v, int with_targ
     e->use();
     e->set_rows(v->n, v->n_global);
     launch_vf_features(v->states, v->obs_dim, v->ld_states, v->old_dist, v->n_actions, v->ld_old, v->episode_starts,
-                       v->n, e->lastpos, e->pos_ws, e->feat, e->Fp, e->stream);
+                       v->n, e->lastpos, e->pos_ws, e->feat, e->Fp, e->stream, v->step_index);
     check_launch();
     if (with_targets) {
       REQUIRE(v->returns, "view has no returns");

@@ -81,10 +81,12 @@ __global__ void __launch_bounds__(256) pos_blocks_kernel(int64_t* blockmax, int 
   }
 }
 
-// feat[r] = [obs[r] | dist[r] | f32(t/10.0)], t = r - (start of r's path); padding zero
+// feat[r] = [obs[r] | dist[r] | f32(t/10.0)], t = r - (start of r's path), or step_index[r] when that is given (a
+// segment rollout's feed: its first path may continue an episode); padding zero
 __global__ void __launch_bounds__(256) features_kernel(const float* obs, int obs_dim, int ld_obs, const float* dist,
                                                        int A, int ld_dist, const int64_t* lastpos,
-                                                       const int64_t* blockpre, int64_t n, float* feat, int Fp) {
+                                                       const int64_t* blockpre, int64_t n, float* feat, int Fp,
+                                                       const int64_t* step_index) {
   const int64_t total = n * Fp;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = e / Fp;
@@ -101,8 +103,8 @@ __global__ void __launch_bounds__(256) features_kernel(const float* obs, int obs
         const int64_t bp = blockpre[r / kPosBlock];
         s = s > bp ? s : bp;
       }
-      const int64_t t = r - (s < 0 ? 0 : s);
-      v = (float)((double)t / 10.0);   // np.arange(l)/10.0 (f64) fed to a float32 placeholder (utils.py:76-77)
+      const int64_t t = step_index ? step_index[r] : r - (s < 0 ? 0 : s);
+      v = (float)((double)t / 10.0);  // np.arange(l)/10.0 (f64) fed to a float32 placeholder (utils.py:76-77)
     }
     feat[e] = v;
   }
@@ -232,16 +234,17 @@ size_t vf_pos_workspace_bytes(int64_t n) { return (size_t)((n + kPosBlock - 1) /
 
 void launch_vf_features(const float* obs, int obs_dim, int ld_obs, const float* dist, int A, int ld_dist,
                         const uint8_t* starts, int64_t n, int64_t* lastpos, void* ws, float* feat, int Fp,
-                        hipStream_t s) {
+                        hipStream_t s, const int64_t* step_index) {
   if (n <= 0) return;
   int64_t* blockpre = static_cast<int64_t*>(ws);
+  if (step_index) starts = nullptr;   // t is given: no path-start scan
   if (starts) {
     const int nb = (int)((n + kPosBlock - 1) / kPosBlock);
     hipLaunchKernelGGL(pos_local_kernel, dim3(nb), dim3(256), 0, s, starts, n, lastpos, blockpre);
     hipLaunchKernelGGL(pos_blocks_kernel, dim3(1), dim3(256), 0, s, blockpre, nb);
   }
   hipLaunchKernelGGL(features_kernel, dim3(grid_of(n * Fp)), dim3(256), 0, s, obs, obs_dim, ld_obs, dist, A, ld_dist,
-                     starts ? lastpos : nullptr, blockpre, n, feat, Fp);
+                     starts ? lastpos : nullptr, blockpre, n, feat, Fp, step_index);
 }
 
 void launch_vf_tail_features(const float* obs, int obs_dim, const float* dist, int A, const int64_t* lengths,

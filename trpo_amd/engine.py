@@ -533,9 +533,10 @@ class Engine:
                              train, time_limit, reset_uniforms, action_uniforms, max_episodes_per_env)
 
     def _rollout(self, fn, ids, info, eid, p, n_envs, n_timesteps, max_pathlength, seed, train, time_limit,
-                 reset_uniforms, action_draws, max_episodes_per_env):
+                 reset_uniforms, action_draws, max_episodes_per_env, after=()):
         """Stage a rollout's parameters into p (time_limit=None keeps p's) and call the entry point `fn` with the
-        environment ids it takes; `info` is the table lookup of eid's kind."""
+        environment ids it takes (and, after p, a segment call's `resume`); `info` is the table lookup of eid's
+        kind."""
         p.n_envs, p.n_timesteps, p.max_pathlength = int(n_envs), int(n_timesteps), int(max_pathlength)
         p.seed, p.train = int(seed) & ((1 << 64) - 1), int(bool(train))
         if time_limit is not None:
@@ -553,7 +554,7 @@ class Engine:
             p.action_uniforms = ad.ptr
             p.mem = ad.mem
         n, paths = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(getattr(lib, fn)(self._h, *ids, ctypes.byref(p), ctypes.byref(n), ctypes.byref(paths)), fn)
+        check(getattr(lib, fn)(self._h, *ids, ctypes.byref(p), *after, ctypes.byref(n), ctypes.byref(paths)), fn)
         self.rollout_steps, self.rollout_paths = n.value, paths.value
         self.rollout_state_dim = info(eid)["state_dim"]
         self._tail_ptr = None
@@ -715,6 +716,83 @@ class Engine:
         check(lib.trpo_rollout_gaussian_to_batch(self._h, ng), "trpo_rollout_gaussian_to_batch")
         self.n, self.n_global = N, ng
         self._tail_ptr = None
+
+    # ------------------------------------------------------------------ fixed-horizon segment rollouts
+    def rollout_segment(self, env="CartPole-v0", n_envs: int = 1, horizon: int = 1000, resume: bool = False,
+                        seed: int = 1, train: bool = True, max_pathlength: int = 1000,
+                        time_limit: Optional[int] = None, reset_uniforms=None, action_uniforms=None,
+                        max_episodes_per_env: int = 0):
+        """A segment rollout (include/trpo_engine.h, trpo_rollout_env_segment): each of n_envs environments takes
+        exactly `horizon` steps, from a reset (resume=False) or from where the previous segment call left it
+        (resume=True: the carry, rollout_carry()).  The fetch and to_batch calls of rollout() then work on it;
+        rollout_segment_fetch() has its own columns.  Draws are indexed per call: injected action_uniforms are
+        [n_envs, horizon], reset_uniforms [n_envs, max_episodes_per_env, reset_draws] with max_episodes_per_env >=
+        horizon + (0 if resume else 1).  Returns (n_envs * horizon, number of paths)."""
+        eid = _env_id(env)
+        p = _lib.RolloutParams()
+        check(lib.trpo_default_rollout_params_env(eid, ctypes.byref(p)), "trpo_default_rollout_params_env")
+        return self._rollout("trpo_rollout_env_segment", (eid,), env_info, eid, p, n_envs, int(n_envs) * int(horizon),
+                             max_pathlength, seed, train, time_limit, reset_uniforms, action_uniforms,
+                             max_episodes_per_env, after=(int(bool(resume)),))
+
+    def rollout_gaussian_segment(self, env="Pendulum-v1", n_envs: int = 1, horizon: int = 1000, resume: bool = False,
+                                 seed: int = 1, train: bool = True, max_pathlength: int = 1000,
+                                 time_limit: Optional[int] = None, reset_uniforms=None, action_normals=None,
+                                 max_episodes_per_env: int = 0):
+        """rollout_segment of a continuous-action environment under this Gaussian engine's policy; injected
+        action_normals are [n_envs, horizon, act_dim]."""
+        cid = _cont_env_id(env)
+        p = _lib.RolloutParams()
+        check(lib.trpo_default_rollout_params_cont(cid, ctypes.byref(p)), "trpo_default_rollout_params_cont")
+        return self._rollout("trpo_rollout_gaussian_segment", (cid,), cont_env_info, cid, p, n_envs,
+                             int(n_envs) * int(horizon), max_pathlength, seed, train, time_limit, reset_uniforms,
+                             action_normals, max_episodes_per_env, after=(int(bool(resume)),))
+
+    def rollout_segment_fetch(self) -> dict:
+        """The segment columns of the last rollout, a segment rollout (host arrays): end_kind u8 [P] (0 terminated,
+        1 cut by the time limit or max_pathlength, 2 cut by the segment), t0 i64 [P] (the episode step index of
+        each path's first row), episode_returns f64 [P] (the episode's return at the path's end, earlier segments
+        included) and step_index i64 [N]."""
+        P, N = getattr(self, "rollout_paths", None) or 0, getattr(self, "rollout_steps", None) or 0
+        out = {"end_kind": np.empty(P, np.uint8), "t0": np.empty(P, np.int64), "episode_returns": np.empty(P),
+               "step_index": np.empty(N, np.int64)}
+        check(lib.trpo_rollout_segment_fetch(self._h, *(a.ctypes.data_as(ctypes.c_void_p) for a in out.values()),
+                                             MEM_HOST), "trpo_rollout_segment_fetch")
+        return out
+
+    def rollout_carry(self) -> dict:
+        """The segment rollouts' carry (host copies): env (the id), n_envs, states f64 [n_envs, state_dim], t i64
+        [n_envs] (steps taken in each environment's current episode) and returns f64 [n_envs] (its rewards so
+        far).  A state error when there is none."""
+        env, n = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib.trpo_rollout_carry_get(self._h, ctypes.byref(env), ctypes.byref(n), None, None, None, MEM_HOST),
+              "trpo_rollout_carry_get")
+        info = (cont_env_info if self._gaussian else env_info)(env.value)
+        out = {"env": env.value, "n_envs": n.value, "states": np.empty((n.value, info["state_dim"])),
+               "t": np.empty(n.value, np.int64), "returns": np.empty(n.value)}
+        check(lib.trpo_rollout_carry_get(self._h, None, None, *(out[k].ctypes.data_as(ctypes.c_void_p)
+                                                                 for k in ("states", "t", "returns")), MEM_HOST),
+              "trpo_rollout_carry_get")
+        return out
+
+    def set_rollout_carry(self, env, states, t, returns):
+        """Install a carry for rollout_segment(resume=True): states [n_envs, state_dim] f64, t [n_envs] and returns
+        [n_envs] of `env`, a name (or id) of this engine's kind of environment."""
+        eid = (_cont_env_id if self._gaussian else _env_id)(env)
+        s = np.ascontiguousarray(states, np.float64)
+        s = s.reshape(1, -1) if s.ndim == 1 else s
+        tt, rr = np.ascontiguousarray(t, np.int64).reshape(-1), np.ascontiguousarray(returns, np.float64).reshape(-1)
+        if not (s.ndim == 2 and s.shape[0] == tt.shape[0] == rr.shape[0]):
+            raise ValueError("set_rollout_carry: states [n_envs, state_dim], t [n_envs] and returns [n_envs]")
+        sd = (cont_env_info if self._gaussian else env_info)(eid)["state_dim"]
+        if s.shape[1] != sd:
+            raise ValueError(f"set_rollout_carry: states must have {sd} columns")
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        check(lib.trpo_rollout_carry_set(self._h, eid, s.shape[0], ptr(s), ptr(tt), ptr(rr), MEM_HOST),
+              "trpo_rollout_carry_set")
+
+    def clear_rollout_carry(self):
+        check(lib.trpo_rollout_carry_clear(self._h), "trpo_rollout_carry_clear")
 
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on: bool = True):
